@@ -1,6 +1,13 @@
 """Benchmark: license files scored/sec vs all templates (Dice), % of HBM roofline.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--config 2|3|4|5] [--files-per-gpu F]
+                    [--dump-outputs DIR] [--full]
+
+A plain run sets the workload up, runs W untimed and K timed steps, writes the last step's results
+under DIR when --dump-outputs is given (float64 .npy files, the same files and so the same results
+from run to run) and prints the result line: value, ms_per_step (wall milliseconds per timed step)
+and roofline. Everything else below -- the result gathers, cpu_baseline, parity, extras -- is
+measured only with --full.
 
 Default workload (BASELINE.json configs[1], "config2"): 1,000,000 synthetic perturbed
 LICENSE files per GPU scored against the 47 vendored choosealicense.com templates
@@ -601,6 +608,27 @@ def abi_sharded_leg(run, args, n_dev, reps=3):
     return rec
 
 
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(path, arrays):
+    """--dump-outputs: the last timed step's results as `path`/<name>.npy, float64 (exact for the
+    int32 / uint32 results). `arrays` maps a name to an array whose first axis is the file index.
+    More than DUMP_MAX_BYTES in all: the same seeded sample of the files for every array, their
+    indices beside them as sample_rows.npy."""
+    os.makedirs(path, exist_ok=True)
+    n = len(next(iter(arrays.values())))
+    per_file = sum(8 * int(np.prod(a.shape[1:], dtype=np.int64)) for a in arrays.values())
+    rows = None
+    if n * per_file > DUMP_MAX_BYTES:
+        keep = DUMP_MAX_BYTES // (per_file + 8)
+        rows = np.sort(np.random.default_rng(20250202).choice(n, keep, replace=False))
+        np.save(os.path.join(path, 'sample_rows.npy'), rows.astype(np.float64))
+    for name, a in arrays.items():
+        np.save(os.path.join(path, f'{name}.npy'), (a if rows is None else a[rows]).astype(np.float64))
+    log(f'dumped {sorted(arrays)} of {n if rows is None else len(rows)} of {n} files to {path}')
+
+
 def free_port():
     import socket
     s = socket.socket()
@@ -659,7 +687,27 @@ def main():
     ap.add_argument('--no-extras', action='store_true',
                     help='skip the separately reported host-side rates (PCIe end-to-end, host prep, single-file '
                          'calls): profiling runs then trace only the timed workload')
+    ap.add_argument('--full', action='store_true',
+                    help='also measure and check everything beside the headline figure: the result gathers, the '
+                         'host-side and end-to-end rates, single-file calls, the one-process sharded entry point, '
+                         'the CPU baseline and oracle parity, and the other configs (each still has its own switch: '
+                         '--no-extras, --shard-mode, --no-cpu-baseline, --extra-configs). Without it a run sets '
+                         'up, warms up, times the steps and prints the result line')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help="write the last timed step's results (rank 0's shard) as DIR/<name>.npy, float64: best, "
+                         'overlap, score per file, or for configs 5 and 5-T600 overlap_matrix, score_matrix, '
+                         'topk_index, topk_score; at most 64 MB in all (a fixed seeded sample of the files beyond)')
     args = ap.parse_args()
+    if args.dump_outputs and args.probe:
+        ap.error('--probe computes no results: nothing for --dump-outputs to write')
+    if args.steps < 1:
+        ap.error('--steps must be at least 1')
+    if not args.full:
+        if args.shard_mode == 'abi':
+            ap.error('--shard-mode abi is one of the legs behind --full')
+        args.no_extras = args.no_cpu_baseline = True
+        args.extra_configs = ''
+        args.shard_mode = 'ranks'
 
     if args.gpus > 1 and 'RANK' not in os.environ:
         sys.exit(self_launch(args.gpus, sys.argv[1:]))
@@ -728,13 +776,20 @@ def main():
         extras['process_group'] = {'backend': group.backend, 'world_size': dist.get_world_size(),
                                    'devices_visible': n_dev, 'ranks_per_device': -(-local_world // max(n_dev, 1))}
     best = ov = score = None
-    if not matrix_mode:
+    if not matrix_mode and args.full:
         t_g = time.perf_counter()
         best, ov, score = batch.download_match(sptr)
         extras['host_gather_ms'] = (time.perf_counter() - t_g) * 1e3
         extras['matches'] = int(group.reduce([int((best >= 0).sum())], 'sum')[0])
         if distributed and world > 1:
             extras.update(gather_compare(batch, group, rank, world, n_per, best, ov, score, sptr))
+    if args.dump_outputs and rank == 0:     # before any later leg scores the batch again
+        if matrix_mode:
+            names = ('overlap_matrix', 'score_matrix', 'topk_index', 'topk_score')
+            dump_outputs(args.dump_outputs, dict(zip(names, batch.download_matrix(args.topk, sptr))))
+        else:
+            res = (best, ov, score) if best is not None else batch.download_match(sptr)
+            dump_outputs(args.dump_outputs, dict(zip(('best', 'overlap', 'score'), res)))
     # ---- separately reported rates (never `value`): PCIe-inclusive end-to-end, host prep ----
     if rank == 0 and not matrix_mode and not args.probe and not args.no_extras:
         torch.cuda.synchronize()

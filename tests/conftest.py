@@ -7,7 +7,11 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
 
-REFERENCE = os.environ.get('LICENSEE_REFERENCE', '/root/reference')
+# the reference's raw data files the tests read (fixture license files, detect.json,
+# license-hashes.json, the 47 choosealicense.com templates and their SPDX XMLs), archived at their paths
+# in a reference checkout by tests/golden/make_golden.py; LICENSEE_REFERENCE names a whole checkout to
+# read instead
+REFERENCE_ARCHIVE = os.path.join(ROOT, 'tests', 'golden', 'reference.tar.xz')
 
 
 def pytest_configure(config):
@@ -30,7 +34,12 @@ def pytest_sessionstart(session):
 
 
 @pytest.fixture(scope='session')
-def reference_root():
-    if not os.path.isdir(os.path.join(REFERENCE, 'spec', 'fixtures')):
-        pytest.skip('reference checkout not present (GPU box / CI without /root/reference)')
-    return REFERENCE
+def reference_root(tmp_path_factory):
+    ref = os.environ.get('LICENSEE_REFERENCE')
+    if ref:
+        return ref
+    import tarfile
+    dst = tmp_path_factory.mktemp('reference')
+    with tarfile.open(REFERENCE_ARCHIVE) as tar:
+        tar.extractall(dst, **({'filter': 'data'} if hasattr(tarfile, 'data_filter') else {}))
+    return str(dst)

@@ -13,6 +13,8 @@ reference's own tests state. Outputs:
                                   key / matcher / SHA1 (spec/fixtures/fixtures.yml).
   fixture_files.json           -- for each fixture license file: normalized text, CC flag,
                                   our SHA1, and the expectations above.
+  reference.tar.xz             -- the raw files behind them that tests normalize again (fixture
+                                  license files, templates, SPDX XMLs, detect.json, license-hashes.json).
   dice_spec.json               -- spec/licensee/matchers/dice_matcher_spec.rb cases.
   vendored.json                -- spec/vendored_license_spec.rb property cases for all 47
                                   templates (rendered / rewrapped / title variants /
@@ -86,6 +88,26 @@ def file_record(text, filename='LICENSE'):
             'sha1': lf.content_hash(), 'wordset_size': len(lf.wordset()), 'length': lf.length()}
 
 
+def write_reference_archive(ref, records):
+    """reference.tar.xz: the raw data files of the checkout that CPU tests read (conftest.py's
+    reference_root unpacks it), at their paths in the checkout -- every supported fixture license
+    file, detect.json, license-hashes.json, the 47 choosealicense.com templates and SPDX XMLs.
+    Sorted members without times or owners: the same bytes from the same checkout."""
+    import tarfile
+    rel = [os.path.join('spec', 'fixtures', r['fixture'], r['file']) for r in records if 'unsupported' not in r]
+    rel += [os.path.join('spec', 'fixtures', f) for f in ('detect.json', 'license-hashes.json')]
+    for sub in (os.path.join('vendor', 'choosealicense.com', '_licenses'),
+                os.path.join('vendor', 'license-list-XML', 'src')):
+        rel += [os.path.join(sub, f) for f in os.listdir(os.path.join(ref, sub))]
+
+    def plain(ti):
+        ti.mtime, ti.uid, ti.gid, ti.uname, ti.gname, ti.mode = 0, 0, 0, '', '', 0o644
+        return ti
+    with tarfile.open(os.path.join(HERE, 'reference.tar.xz'), 'w:xz') as tar:
+        for p in sorted(set(rel)):
+            tar.add(os.path.join(ref, p), arcname=p, filter=plain)
+
+
 def main(ref):
     corpus = load_raw_corpus(ref)
     License.set_corpus(corpus)
@@ -124,6 +146,7 @@ def main(ref):
             records.append(rec)
     with open(os.path.join(HERE, 'fixture_files.json'), 'w') as fh:
         json.dump(records, fh, indent=1, sort_keys=True, ensure_ascii=False)
+    write_reference_archive(ref, records)
 
     # ---- dice_matcher_spec.rb ----------------------------------------------------------
     gpl, mit, cc_by = License.find('gpl-3.0'), License.find('mit'), License.find('cc-by-4.0')

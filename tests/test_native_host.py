@@ -2,7 +2,7 @@
 
 Both run the same compiled patterns (content_helper.py); this checks the C++ op sequence,
 regex engine, decoding and interning against the Python path on the reference's fixtures,
-every vendored-license property text, all 47 raw template bodies (reference present), and
+every vendored-license property text, all 47 raw template bodies (tests/golden/reference.tar.xz), and
 seeded fuzz texts built from markup fragments the normalizer handles.
 """
 import json

@@ -5,7 +5,7 @@
   spec/fixtures/detect.json              (normalized MIT text)
   spec/licensee/content_helper_spec.rb   (strip / normalize / title-regex cases)
   spec/licensee/project_files/license_file_spec.rb:49-57 (93 words, first 'permission')
-Tests reading the raw reference tree skip when it is absent (GPU box).
+Tests reading raw reference files read the copies in tests/golden/reference.tar.xz.
 """
 import hashlib
 import json

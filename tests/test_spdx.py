@@ -1,7 +1,7 @@
 """SPDX license-list-XML ingestion (licensee_amd/spdx.py).
 
-CPU: the vendored data file equals a fresh ingestion of the reference's 47 XMLs (when the
-reference tree is present), every alt-segment count equals license.rb:273-283's regex rule
+CPU: the vendored data file equals a fresh ingestion of the reference's 47 XMLs (stored in
+tests/golden/reference.tar.xz), every alt-segment count equals license.rb:273-283's regex rule
 restated in license.py, the XML markup is gone from every text, and each SPDX text is close to
 its choosealicense.com template under the oracle's Dice similarity.
 GPU (-m gpu): each SPDX text, read as a LICENSE file, is Dice-matched through the product path
@@ -19,8 +19,6 @@ import pytest
 from licensee_amd import spdx
 from licensee_amd.license import License, spdx_alt_segments_from_xml
 
-REF_SPDX = '/root/reference/vendor/license-list-XML/src'
-
 # SPDX texts whose Dice match (threshold 98) is not their own choosealicense.com key, with the
 # reason (scores asserted in the GPU test)
 NOT_DETECTED = {
@@ -33,15 +31,14 @@ NOT_DETECTED = {
 }
 
 
-def test_data_file_matches_reference_xml():
-    if not os.path.isdir(REF_SPDX):
-        pytest.skip('reference tree absent')
-    fresh = spdx.ingest_dir(REF_SPDX)
+def test_data_file_matches_reference_xml(reference_root):
+    ref_spdx = os.path.join(reference_root, 'vendor', 'license-list-XML', 'src')
+    fresh = spdx.ingest_dir(ref_spdx)
     stored = [{'id': t.spdx_id, 'name': t.title, 'text': t.content, 'alt_segments': t.spdx_alt_segments()}
               for t in spdx.load()]
     assert fresh == stored
-    for fn in sorted(os.listdir(REF_SPDX)):
-        with open(os.path.join(REF_SPDX, fn), encoding='utf-8', newline='') as fh:
+    for fn in sorted(os.listdir(ref_spdx)):
+        with open(os.path.join(ref_spdx, fn), encoding='utf-8', newline='') as fh:
             raw = fh.read()
         rec = spdx.license_info_from_xml(raw)
         assert rec['alt_segments'] == spdx_alt_segments_from_xml(raw)

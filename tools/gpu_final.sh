@@ -1,6 +1,6 @@
 #!/bin/bash
 # A round's final measurement set, over two leases (each call stays inside gpurun's 20-minute limit):
-#   bash tools/gpu_final.sh <tag> a   -- the GPU suite + smoke (gpu_tests.sh), the default bench line,
+#   bash tools/gpu_final.sh <tag> a   -- the GPU suite + smoke (gpu_tests.sh), the bench.py --full line,
 #                                        the same-lease trace of config 2, profiles of configs 2 and 3
 #                                        (config 3 through dice_batch_match_confidence)  [gpu_measure.sh]
 #   bash tools/gpu_final.sh <tag> b   -- profiles of configs 4, 5, 3-top1 (dice_batch_match), 3 on the

@@ -1,6 +1,6 @@
 #!/bin/bash
 # One GPU session = one self-consistent measurement set (tag e.g. r2a):
-#   1. the driver's default bench line (config 2 + extras.configs 3/4/5, CPU baseline, parity);
+#   1. the driver's bench.py --full line (config 2 + extras.configs 3/4/5, CPU baseline, parity);
 #   2. rocprofv3 --kernel-trace --stats of the SAME primary workload and step count
 #      (bench.py --extra-configs= --no-cpu-baseline), so profiles/<tag>_config2 kernel averages
 #      and the bench line's launch_ms come from one lease;
@@ -12,7 +12,8 @@ TAG=$1
 CONFIGS=${2:-2 3 4 5}
 export TMPDIR=/tmp
 mkdir -p gpurun_out
-timeout -k 10 600 python bench.py > gpurun_out/${TAG}_bench.json 2> gpurun_out/${TAG}_bench.err || exit 11
+RES=$_    # the results folder made above
+timeout -k 10 600 python bench.py --full > $RES/${TAG}_bench.json 2> $RES/${TAG}_bench.err || exit 11
 cat gpurun_out/${TAG}_bench.json
 OUT=gpurun_out/prof_${TAG}_same
 mkdir -p $OUT

@@ -2,7 +2,7 @@
 
     python tools/summarize_session.py <tag>
 
-Reads gpurun_out/<tag>_bench.json (the default bench line) and gpurun_out/prof_<tag>_same/
+Reads, from the session's output folder, <tag>_bench.json (the bench.py --full line) and prof_<tag>_same/
 (rocprofv3 --kernel-trace --stats of the same primary workload and step count, same lease) and
 writes profiles/<tag>_bench.json plus profiles/<tag>_session.md: the trace's product-kernel
 average beside the bench's launch_ms / ms_per_step, and roofline.frac recomputed from the
@@ -41,7 +41,7 @@ def main():
     with open(os.path.join(ROOT, 'profiles', f'{tag}_session.md'), 'w') as fh:
         fh.write(f'# Session {tag}: bench line + same-lease rocprofv3 trace\n\n')
         fh.write('Commands (one gpurun call, `tools/gpu_measure.sh {0}`):\n\n'
-                 '1. `python bench.py` -> `profiles/{0}_bench.json`\n'
+                 '1. `python bench.py --full` -> `profiles/{0}_bench.json`\n'
                  '2. `rocprofv3 --kernel-trace --stats -- python bench.py --extra-configs= --no-cpu-baseline` '
                  '(same primary workload and step count)\n\n'.format(tag))
         fh.write('| | value |\n|---|---|\n')
