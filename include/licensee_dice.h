@@ -267,6 +267,20 @@ int dice_precompile(const dice_templates *templates, char *path, int32_t path_ca
 /* Generated HIP source of the sparse program (introspection/tests). Returns its length,
  * writes at most cap-1 bytes + NUL when buf != NULL, or -1 on bad input. */
 int64_t dice_program_source(const dice_templates *templates, char *buf, int64_t cap);
+/* The same for the program over the compact tile (the default of dice_create for corpora of at
+ * most 64 templates; the environment variable DICE_PROG_LAYOUT=bits, read at dice_create, keeps
+ * the full-bitset tile of dice_program_source). Same contract; -1 also for more templates. */
+int64_t dice_program_source_compact(const dice_templates *templates, char *buf, int64_t cap);
+/* The compact tile's layout, a pure function of `templates`. Vocabulary words that belong to
+ * exactly the same templates form a class; a large class is stored as byte counts of at most 255
+ * words each, the other words of some template as bits in vocabulary order. dest[V] (may be
+ * NULL): per word its bit position in the tile (>= 0), -1 for a word of no template (not in
+ * the tile), or -2 - f for count byte f, which is tile byte *count_base + f. The tile is
+ * bit dwords, then count bytes, zero-padded to whole 16-byte quads; resident tile slot i holds
+ * quad qperm[i] of it (qperm may be NULL; qperm_cap entries available). Returns the tile's
+ * quad count, or -1 on bad input or too small a qperm_cap. */
+int32_t dice_program_layout(const dice_templates *templates, int32_t *dest, int32_t *count_base,
+                            int32_t *qperm, int32_t qperm_cap);
 
 const char *dice_last_error(void);
 

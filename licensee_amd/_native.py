@@ -30,6 +30,7 @@ EXPORTED_SYMBOLS = (
     'dice_match_confidence', 'dice_batch_match_confidence', 'dice_match_sharded_confidence',
     'dice_batch_scored_pairs', 'dice_vocab_setup', 'dice_batch_upload_text', 'dice_batch_set_rows',
     'dice_batch_download_rows', 'dice_host_alloc', 'dice_host_free',
+    'dice_program_source_compact', 'dice_program_layout',
 )
 DICE_GATHER_HOST = 0
 DICE_GATHER_DEVICE = 1
@@ -192,6 +193,8 @@ def load_library(path: str = LIB_PATH) -> ctypes.CDLL:
         'dice_batch_scored_pairs': (ctypes.c_int, [vp, ctypes.POINTER(i64), vp]),
         'dice_precompile': (ctypes.c_int, [ctypes.POINTER(_Templates), ctypes.c_char_p, i32]),
         'dice_program_source': (i64, [ctypes.POINTER(_Templates), ctypes.c_char_p, i64]),
+        'dice_program_source_compact': (i64, [ctypes.POINTER(_Templates), ctypes.c_char_p, i64]),
+        'dice_program_layout': (i32, [ctypes.POINTER(_Templates), vp, vp, vp, i32]),
         'dice_exact_setup': (ctypes.c_int, [vp, vp, vp, vp]),
         'dice_batch_exact': (ctypes.c_int, [vp, vp, vp]),
         'dice_batch_download_exact': (ctypes.c_int, [vp, vp, vp]),

@@ -331,16 +331,24 @@ int dice::upload_tail(dice_batch* b, int64_t n, const uint32_t* wf, const int32_
 }
 
 // The tile-layout kernels' repack of the batch's row-major bitsets (kinds 0-2).
+static int launch_pack(dice_ctx* c, dice_batch* b, int64_t n, hipStream_t s) {
+    const int64_t n_tiles = (n + kWave - 1) / kWave;
+    if (n_tiles == 0) return DICE_OK;
+    if (c->prog_pack) return dice::program_launch_pack(c, b, n, s);   // sparse program, compact tile
+    {
+        const int64_t total = n_tiles * c->wq * kWave;
+        const unsigned grid = (unsigned)((total + kBlock - 1) / kBlock);
+        hipLaunchKernelGGL(dice_pack_tiles, dim3(grid), dim3(kBlock), 0, s, b->d_rows, n, c->w64, c->wq,
+                           c->kind == 1 ? (const int32_t*)c->d_qperm : nullptr, b->d_tiles, n_tiles);
+    }
+    HIP_TRY(hipGetLastError());
+    return DICE_OK;
+}
+
 int dice::repack(dice_batch* b, hipStream_t s) {
     dice_ctx* c = b->ctx;
     if (c->kind == 3 || b->n == 0) return DICE_OK;
-    const int64_t n_tiles = (b->n + kWave - 1) / kWave;
-    const int64_t total = n_tiles * c->wq * kWave;
-    const unsigned grid = (unsigned)((total + kBlock - 1) / kBlock);
-    hipLaunchKernelGGL(dice_pack_tiles, dim3(grid), dim3(kBlock), 0, s, b->d_rows, b->n, c->w64, c->wq,
-                       c->kind == 1 ? (const int32_t*)c->d_qperm : nullptr, b->d_tiles, n_tiles);
-    HIP_TRY(hipGetLastError());
-    return DICE_OK;
+    return launch_pack(c, b, b->n, s);
 }
 
 extern "C" {
@@ -440,6 +448,7 @@ int dice_create(const dice_templates* t, int32_t device, dice_ctx** out) {
     c->V = t->n_vocab;
     c->w64 = dice_words64(t->n_vocab);
     c->wq = (c->w64 + 1) / 2;
+    c->twq = c->wq;
     c->tpad = ((c->T + kTT - 1) / kTT) * kTT;
     c->h_lf.assign(t->lf_bits, t->lf_bits + (size_t)c->T * c->w64);   // Exact tables (dice_exact.hip)
     int rc;
@@ -548,7 +557,7 @@ int dice_batch_create(dice_ctx* ctx, int64_t capacity, dice_batch** out) {
     const int64_t npad = b->n_tiles_cap * kWave;
     int rc;
     if ((rc = dalloc(&b->d_rows, (size_t)capacity * ctx->w64)) ||
-        (rc = dalloc(&b->d_tiles, (size_t)b->n_tiles_cap * ctx->wq * kWave)) ||
+        (rc = dalloc(&b->d_tiles, (size_t)b->n_tiles_cap * ctx->twq * kWave)) ||
         (rc = dalloc(&b->d_wf, npad)) || (rc = dalloc(&b->d_len, npad)) || (rc = dalloc(&b->d_cc, npad)) ||
         (rc = dalloc(&b->d_best, npad)) || (rc = dalloc(&b->d_ov, npad)) || (rc = dalloc(&b->d_score, npad)) ||
         (ctx->prune && (rc = dice::prune_reserve(ctx, b)))) {
@@ -562,7 +571,7 @@ int dice_batch_create(dice_ctx* ctx, int64_t capacity, dice_batch** out) {
 
 int64_t dice_batch_bytes_per_file(const dice_batch* b) {
     if (!b) return -1;
-    return (int64_t)b->ctx->wq * 16;
+    return (int64_t)b->ctx->twq * 16;
 }
 
 int dice_batch_upload(dice_batch* b, const dice_files* f, void* stream) {
@@ -831,7 +840,7 @@ int dice_batch_stream_probe(dice_batch* b, void* stream) {
     const int64_t n_tiles = (b->n + kWave - 1) / kWave;
     const unsigned grid = (unsigned)((n_tiles + (kBlock / kWave) - 1) / (kBlock / kWave));
     // results land in the (16 B/file) score+best+overlap area: reuse d_score as scratch
-    hipLaunchKernelGGL(dice_stream_probe, dim3(grid), dim3(kBlock), 0, s, b->d_tiles, b->n, c->wq,
+    hipLaunchKernelGGL(dice_stream_probe, dim3(grid), dim3(kBlock), 0, s, b->d_tiles, b->n, c->twq,
                        reinterpret_cast<uint4*>(b->d_rows));
     HIP_TRY(hipGetLastError());
     return DICE_OK;
@@ -996,13 +1005,7 @@ int small_upload(dice_ctx* c, dice_batch* b, const dice_files* f, const SmallLay
             for (int64_t i = 0; i < n; ++i) b->n_long += f->wordset_size[i] > c->prune_max_lf;
         return DICE_OK;
     }
-    const int64_t n_tiles = npad / kWave;
-    const int64_t total = n_tiles * c->wq * kWave;
-    hipLaunchKernelGGL(dice_pack_tiles, dim3((unsigned)((total + kBlock - 1) / kBlock)), dim3(kBlock), 0, c->stream,
-                       b->d_rows, n, c->w64, c->wq, c->kind == 1 ? (const int32_t*)c->d_qperm : nullptr, b->d_tiles,
-                       n_tiles);
-    HIP_TRY(hipGetLastError());
-    return DICE_OK;
+    return launch_pack(c, b, n, c->stream);
 }
 
 int small_match(dice_ctx* c, const dice_files* f, double thr, int32_t* best, uint32_t* ov, double* score,

@@ -66,6 +66,10 @@ struct dice_ctx {
     hipFunction_t prog_matrix = nullptr;    // top-k <= 4
     hipFunction_t prog_matrix16 = nullptr;  // top-k <= 16
     int32_t* d_qperm = nullptr;             // sparse program tile slot -> vocabulary quad (kind 1)
+    // Quads per file of the resident tile: wq (the row's quads) except for the sparse program's
+    // compact tile, which the generated dice_pack_compact fills (dice_program.cpp).
+    int32_t twq = 0;
+    hipFunction_t prog_pack = nullptr;      // compact tile only
     dice_batch* scratch = nullptr;  // reused by the host-buffer calls
     // kind 2 plan (dice_lds.hip): per-(slab, template) entry runs, entries, wave split
     void* d_lrec = nullptr;

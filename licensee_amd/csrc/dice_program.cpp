@@ -16,6 +16,11 @@
 // envelope (|W_F| >= 2^20 or len_F >= 2^21, or a corpus outside the envelope) run the same
 // program with IEEE-double compares (see dice_common.h for why both orders coincide).
 //
+// By default the program runs over the compact tile (derive_layout below):
+// words that belong to exactly the same templates are interchangeable for every overlap, so a
+// large class of them is a byte count (v_and_b32 literal + v_sad_u8) instead of bits, and the
+// file's tile is half as long. DICE_PROG_LAYOUT=bits keeps the full-bitset tile.
+//
 // The source is compiled with hiprtc for gfx950 and cached by hash under the library
 // directory (lib/cache/dice_prog_<hash>.co), so a corpus compiles once per machine image.
 #include <hip/hip_runtime.h>
@@ -113,6 +118,18 @@ __device__ __forceinline__ bool ge(u32 oa, i32 da, u32 ob, i32 db) {
 }
 #define ACC(d, m) a = __builtin_popcount(f[d] & (m##u)) + a
 #define ACCF(d) a = __builtin_popcount(f[d]) + a
+)HIP";
+
+// Compact tile only: masked four-byte sum of a count dword (v_and_b32 literal + v_sad_u8 against
+// 0, accumulating); the plain-C form serves the host tests.
+const char* kCompactPrelude = R"HIP(
+#ifndef __HIP_DEVICE_COMPILE__
+__device__ __forceinline__ u32 bytesum(u32 x) { return (x & 0xffu) + ((x >> 8) & 0xffu) + ((x >> 16) & 0xffu) + (x >> 24); }
+#else
+__device__ __forceinline__ u32 bytesum(u32 x) { u32 r; asm("v_sad_u8 %0, %1, 0, 0" : "=v"(r) : "v"(x)); return r; }
+#endif
+#define ACCS(acc, x, MASK) acc = bytesum((x) & (MASK)) + acc
+#define ACCSF1(acc, x) acc = bytesum(x) + acc
 )HIP";
 
 const char* kMatchKernel = R"HIP(
@@ -279,9 +296,10 @@ static void build_entries(const dice_templates* t, int32_t w64, Program& p) {
 static std::string acc_stmt(const Entry& en) {
     std::ostringstream o;
     if (en.mask == 0xFFFFFFFFu)
-        o << "ACCF1(acc[" << en.tpl << "], f[" << en.dword % 4 << "]);\n";
+        o << (en.sum ? "ACCSF1" : "ACCF1") << "(acc[" << en.tpl << "], f[" << en.dword % 4 << "]);\n";
     else
-        o << "ACCM(acc[" << en.tpl << "], f[" << en.dword % 4 << "], 0x" << std::hex << en.mask << std::dec << ");\n";
+        o << (en.sum ? "ACCS" : "ACCM") << "(acc[" << en.tpl << "], f[" << en.dword % 4 << "], 0x" << std::hex
+          << en.mask << std::dec << ");\n";
     return o.str();
 }
 
@@ -324,7 +342,10 @@ static std::string acc_block(const std::vector<Entry>& dm, size_t b, size_t e) {
             const Entry& en = dm[i];
             std::ostringstream ins;
             const int src = en.mask == 0xFFFFFFFFu ? f_op(en.dword % 4) : tmp0 + (int)(i - g);
-            ins << "v_bcnt_u32_b32 %" << acc_op(en.tpl) << ", %" << src << ", %" << acc_op(en.tpl);
+            if (en.sum)   // count dword: sum of the selected bytes
+                ins << "v_sad_u8 %" << acc_op(en.tpl) << ", %" << src << ", 0, %" << acc_op(en.tpl);
+            else
+                ins << "v_bcnt_u32_b32 %" << acc_op(en.tpl) << ", %" << src << ", %" << acc_op(en.tpl);
             emit(ins.str());
         }
         for (size_t i = g; i < ge; ++i) c << acc_stmt(dm[i]);
@@ -365,11 +386,15 @@ static void emit_macro(std::ostringstream& s, const std::string& head, const std
 // instructions; the epilogue (denominator, compare) runs once per template after the last quad.
 // (The template-major order, the whole bitset loaded up front and each template retired in turn,
 // measured 2% slower and is retired: DESIGN.md Appendix B.)
-std::string program_source(const dice_templates* t, Program& p, int32_t wq, bool corpus_fast) {
+// `wq` is the tile's quad count; `burst` the quads per load group.
+std::string program_source(const dice_templates* t, Program& p, int32_t wq, bool corpus_fast, int burst = 5) {
     std::ostringstream s;
     s << "#define WPB " << p.wpb << "\n";
     s << "// dice sparse program: T=" << t->n_templates << " V=" << t->n_vocab << " entries=" << p.prog.size()
       << " order=d\n";
+    if (p.compact)
+        s << "// layout=compact threshold=" << p.layout.threshold << " bits=" << p.layout.n_bits
+          << " bit_dwords=" << p.layout.bit_dwords << " count_bytes=" << p.layout.n_fields << " burst=" << burst << "\n";
     s << "#define MATCH_WAVES \n";
     uint32_t max_lf = 0;
     for (int32_t i = 0; i < t->n_templates; ++i) max_lf = std::max(max_lf, t->lf_size[i]);
@@ -380,6 +405,7 @@ std::string program_source(const dice_templates* t, Program& p, int32_t wq, bool
     s << "#define OUT_NT 1\n";
     s << "#define WQ " << wq << "\n#define NT " << t->n_templates << "\n#define CORPUS_FAST "
       << (corpus_fast ? 1 : 0) << "\n#define NARROW_MUL " << (max_lf < (1u << 11) ? 1 : 0) << "\n" << kPrelude;
+    if (p.compact) s << kCompactPrelude;
 
     std::vector<std::string> den(t->n_templates);
     for (int32_t i = 0; i < t->n_templates; ++i) {
@@ -462,7 +488,7 @@ std::string program_source(const dice_templates* t, Program& p, int32_t wq, bool
             // group g+1 is requested (nb contiguous 1 KiB wave loads back to back) before group g
             // is consumed. With non-temporal loads, bursts of 3 measured ~1.5% ahead of an 8-deep
             // ring at 92 instead of 124 VGPRs, 4 another ~3.5%, 5 another 1.8% (6: -0.3%)
-            const int nb = std::max(1, std::min<int>(5, (int)quads.size()));
+            const int nb = std::max(1, std::min<int>(burst, (int)quads.size()));
             const size_t ng = (quads.size() + nb - 1) / nb;
             auto group_loads = [&](std::ostringstream& o, size_t g, int set) {
                 for (size_t i = g * nb; i < std::min(quads.size(), (g + 1) * nb); ++i)
@@ -582,6 +608,302 @@ static std::string source_for(const dice_templates* t, Program& prog) {
     return program_source(t, prog, (w64 + 1) / 2, corpus_in_fast_envelope(t));
 }
 
+// ---------------------------------------------------------------------------------------
+// Compact tile: layout derivation, its program entries and the repack tables
+// ---------------------------------------------------------------------------------------
+
+// Template-membership column of every vocabulary word (bit i: the word is in template i).
+static std::vector<uint64_t> word_columns(const dice_templates* t) {
+    const int32_t V = t->n_vocab, w64 = (V + 63) / 64;
+    std::vector<uint64_t> col((size_t)V, 0);
+    for (int32_t i = 0; i < t->n_templates; ++i) {
+        const uint64_t* row = t->lf_bits + (size_t)i * w64;
+        for (int32_t v = 0; v < V; ++v)
+            if ((row[v >> 6] >> (v & 63)) & 1) col[(size_t)v] |= 1ull << i;
+    }
+    return col;
+}
+
+struct WordClass {
+    uint64_t col;
+    std::vector<int32_t> words;   // ascending
+};
+
+// Places every word for class-size threshold `th`: classes of more than th words become count
+// fields (capacity <= 255, the class's words split evenly in vocabulary order), the other words
+// of some template keep a bit, in vocabulary order. Count fields are grouped four to a dword
+// greedily by template set: a dword starts with the widest remaining set and takes the fields
+// that add the fewest templates to it, so one masked byte sum serves several fields.
+static void place_words(const std::vector<WordClass>& classes, int32_t V, int32_t th, CompactLayout& L) {
+    L.threshold = th;
+    L.dest.assign((size_t)V, -1);
+    struct Field {
+        uint64_t col;
+        std::vector<int32_t> words;
+    };
+    std::vector<Field> raw;
+    std::vector<char> bit((size_t)V, 0);
+    for (const WordClass& c : classes) {
+        const int32_t sz = (int32_t)c.words.size();
+        if (sz <= th) {
+            for (int32_t v : c.words) bit[(size_t)v] = 1;
+            continue;
+        }
+        const int32_t nf = (sz + 254) / 255, cap = (sz + nf - 1) / nf;
+        for (int32_t f = 0; f < nf; ++f) {
+            Field fd{c.col, {}};
+            for (int32_t j = f * cap; j < std::min(sz, (f + 1) * cap); ++j) fd.words.push_back(c.words[(size_t)j]);
+            raw.push_back(std::move(fd));
+        }
+    }
+    L.n_bits = 0;
+    for (int32_t v = 0; v < V; ++v)
+        if (bit[(size_t)v]) L.dest[(size_t)v] = L.n_bits++;
+    L.bit_dwords = (L.n_bits + 31) / 32;
+    L.n_fields = (int32_t)raw.size();
+    L.field_col.clear();
+    std::vector<char> used(raw.size(), 0);
+    auto pc = [](uint64_t x) { return __builtin_popcountll(x); };
+    for (size_t placed = 0; placed < raw.size();) {
+        uint64_t un = 0;
+        for (int k = 0; k < 4 && placed < raw.size(); ++k, ++placed) {
+            size_t pick = raw.size();
+            for (size_t i = 0; i < raw.size(); ++i) {
+                if (used[i]) continue;
+                if (pick == raw.size()) { pick = i; continue; }
+                const bool better = k == 0 ? pc(raw[i].col) > pc(raw[pick].col)
+                                           : pc(un | raw[i].col) < pc(un | raw[pick].col);
+                if (better) pick = i;
+            }
+            used[pick] = 1;
+            un |= raw[pick].col;
+            const int32_t f = (int32_t)L.field_col.size();
+            L.field_col.push_back(raw[pick].col);
+            for (int32_t v : raw[pick].words) L.dest[(size_t)v] = -2 - f;
+        }
+    }
+    const int32_t dwords = L.bit_dwords + (L.n_fields + 3) / 4;
+    L.quads = std::max(1, (dwords + 3) / 4);
+}
+
+// The compact tile's entry list (template-major, dword ascending).
+static void build_compact_entries(const dice_templates* t, const std::vector<uint64_t>& col, const CompactLayout& L,
+                                  std::vector<Entry>& out) {
+    out.clear();
+    const int32_t nd = L.bit_dwords + (L.n_fields + 3) / 4;
+    std::vector<uint32_t> m((size_t)nd);
+    for (int32_t i = 0; i < t->n_templates; ++i) {
+        std::fill(m.begin(), m.end(), 0u);
+        for (int32_t v = 0; v < t->n_vocab; ++v) {
+            const int32_t p = L.dest[(size_t)v];
+            if (p >= 0 && ((col[(size_t)v] >> i) & 1)) m[(size_t)(p >> 5)] |= 1u << (p & 31);
+        }
+        for (int32_t f = 0; f < L.n_fields; ++f)
+            if ((L.field_col[(size_t)f] >> i) & 1) m[(size_t)(L.bit_dwords + f / 4)] |= 0xFFu << (8 * (f % 4));
+        for (int32_t d = 0; d < nd; ++d)
+            if (m[(size_t)d]) out.push_back(Entry{i, d, m[(size_t)d], d >= L.bit_dwords});
+    }
+}
+
+static int64_t entry_cost(const std::vector<Entry>& es) {
+    int64_t c = 0;
+    for (const Entry& e : es) c += e.mask == 0xFFFFFFFFu ? 1 : 2;
+    return c;
+}
+
+// Layout for the corpus: the class-size threshold that gives the fewest tile quads, on a tie the
+// fewest program instructions (then the smallest threshold). A class of <= 8 words never takes
+// more bits as bits than as a count byte, so thresholds start at 8.
+static void derive_layout(const dice_templates* t, CompactLayout& best, std::vector<Entry>& entries) {
+    const int32_t V = t->n_vocab;
+    const std::vector<uint64_t> col = word_columns(t);
+    std::vector<WordClass> classes;
+    {
+        std::vector<int32_t> order;
+        for (int32_t v = 0; v < V; ++v)
+            if (col[(size_t)v]) order.push_back(v);
+        std::stable_sort(order.begin(), order.end(), [&](int32_t a, int32_t b) { return col[(size_t)a] < col[(size_t)b]; });
+        for (int32_t v : order) {
+            if (classes.empty() || classes.back().col != col[(size_t)v]) classes.push_back(WordClass{col[(size_t)v], {}});
+            classes.back().words.push_back(v);
+        }
+    }
+    std::vector<int32_t> ths{8};
+    for (const WordClass& c : classes)
+        if (c.words.size() > 8) ths.push_back((int32_t)c.words.size());
+    std::sort(ths.begin(), ths.end());
+    ths.erase(std::unique(ths.begin(), ths.end()), ths.end());
+    int64_t best_cost = 0;
+    bool have = false;
+    for (int32_t th : ths) {
+        CompactLayout L;
+        std::vector<Entry> es;
+        place_words(classes, V, th, L);
+        build_compact_entries(t, col, L, es);
+        const int64_t cost = entry_cost(es);
+        if (!have || L.quads < best.quads || (L.quads == best.quads && cost < best_cost)) {
+            best = std::move(L);
+            entries.swap(es);
+            best_cost = cost;
+            have = true;
+        }
+    }
+}
+
+// Repack pieces for dice_pack_compact, per tile dword in slot order (p.qperm applied).
+static void build_pack_lists(Program& p, int32_t V) {
+    const CompactLayout& L = p.layout;
+    std::vector<int32_t> slot_of((size_t)L.quads, 0);
+    for (size_t s = 0; s < p.qperm.size(); ++s) slot_of[(size_t)p.qperm[s]] = (int32_t)s;
+    auto tile_dword = [&](int32_t d) { return slot_of[(size_t)(d >> 2)] * 4 + (d & 3); };
+    struct Key {
+        int32_t dst, src, op;
+        bool operator<(const Key& o) const {
+            return dst != o.dst ? dst < o.dst : src != o.src ? src < o.src : op < o.op;
+        }
+    };
+    std::vector<std::pair<Key, uint32_t>> ps;
+    for (int32_t v = 0; v < V; ++v) {
+        const int32_t p0 = L.dest[(size_t)v];
+        if (p0 == -1) continue;
+        Key k;
+        k.src = v >> 5;
+        if (p0 >= 0) {
+            k.dst = tile_dword(p0 >> 5);
+            k.op = (p0 & 31) - (v & 31);
+        } else {
+            const int32_t f = -2 - p0;
+            k.dst = tile_dword(L.bit_dwords + f / 4);
+            k.op = 64 + 8 * (f % 4);
+        }
+        ps.push_back({k, 1u << (v & 31)});
+    }
+    std::stable_sort(ps.begin(), ps.end(), [](const auto& a, const auto& b) { return a.first < b.first; });
+    p.pack_lists.assign((size_t)L.quads * 4, {});
+    for (size_t i = 0; i < ps.size(); ++i) {
+        const Key& k = ps[i].first;
+        std::vector<PackPiece>& l = p.pack_lists[(size_t)k.dst];
+        if (i && !(ps[i - 1].first < k))   // same (dst, src, op): one piece
+            l.back().mask |= ps[i].second;
+        else
+            l.push_back(PackPiece{k.src, ps[i].second, k.op});
+    }
+}
+
+// The repack kernel of the compact tile, generated beside the program (device compile only: the
+// host tests pack their tiles in numpy). One workgroup per 64-file tile stages the tile's rows
+// through LDS with coalesced 8-byte loads (row stride odd in dwords, so the 64 lanes of a wave,
+// one file each, hit distinct banks; rows too long for 64 KiB are read from global memory
+// instead), then each of its four waves builds whole quads -- row dwords at constant LDS
+// offsets, masks and shifts as literals -- and stores one uint4 per lane. Quads are dealt to
+// the waves by piece count, largest first.
+static std::string pack_source(const Program& p, int32_t w64) {
+    const CompactLayout& L = p.layout;
+    int32_t stride = (2 * w64) | 1;
+    if ((size_t)64 * stride * 4 > 64 * 1024) stride = 0;
+    std::ostringstream s;
+    s << "#ifdef __HIP_DEVICE_COMPILE__\n#define PACK_STRIDE " << stride << "\n#define PACK_W64 " << w64 << "\n";
+    s << R"HIP(extern "C" __global__ __launch_bounds__(256) void dice_pack_compact(
+    const u64* __restrict__ rows, i64 n, uint4* __restrict__ tiles) {
+    const i64 tile = blockIdx.x;
+    const int lane = threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    const i64 file0 = tile * 64;
+    const bool valid = file0 + lane < n;
+#if PACK_STRIDE
+    __shared__ u32 lrows[64 * PACK_STRIDE];
+    {
+        const i64 left = n - file0;
+        const int nvalid = left < 64 ? (int)left : 64;
+        const u64* src = rows + file0 * PACK_W64;
+        for (int i = threadIdx.x; i < 64 * PACK_W64; i += 256) {
+            const int f = i / PACK_W64, d = i - f * PACK_W64;
+            const u64 x = f < nvalid ? src[i] : 0ull;
+            lrows[f * PACK_STRIDE + 2 * d] = (u32)x;
+            lrows[f * PACK_STRIDE + 2 * d + 1] = (u32)(x >> 32);
+        }
+        __syncthreads();
+    }
+    const u32* r = lrows + lane * PACK_STRIDE;
+#else
+    const u32* r = (const u32*)(rows + (valid ? file0 + lane : file0) * PACK_W64);
+#endif
+    uint4* out = tiles + tile * (i64)(WQ * 64) + lane;
+#define PC(src, m) ((u32)__builtin_popcount(r[src] & (m)))
+#define PUT(slot, a, b, c, d) out[(slot) * 64] = valid ? make_uint4(a, b, c, d) : make_uint4(0, 0, 0, 0);
+    switch (wave) {
+)HIP";
+    // quads to waves: largest piece count first, to the wave with the least so far
+    std::vector<std::pair<size_t, int32_t>> order;
+    for (int32_t q = 0; q < L.quads; ++q) {
+        size_t np = 0;
+        for (int k = 0; k < 4; ++k) np += p.pack_lists[(size_t)q * 4 + k].size();
+        order.push_back({np, q});
+    }
+    std::stable_sort(order.begin(), order.end(), [](const auto& a, const auto& b) { return a.first > b.first; });
+    std::vector<int32_t> of_wave[4];
+    size_t load[4] = {0, 0, 0, 0};
+    for (const auto& o : order) {
+        const int w = (int)(std::min_element(load, load + 4) - load);
+        of_wave[w].push_back(o.second);
+        load[w] += o.first + 1;
+    }
+    for (int w = 0; w < 4; ++w) {
+        s << "    case " << w << ":\n";
+        for (int32_t q : of_wave[w]) {
+            s << "        PUT(" << q;
+            for (int k = 0; k < 4; ++k) {
+                const std::vector<PackPiece>& l = p.pack_lists[(size_t)q * 4 + k];
+                s << ",\n            ";
+                if (l.empty()) {
+                    s << "0u";
+                } else if (l[0].op >= 64) {   // count dword: popcounts summed per byte
+                    bool first = true;
+                    for (int by = 0; by < 4; ++by) {
+                        std::ostringstream sum;
+                        for (const PackPiece& pc : l) {
+                            if (pc.op != 64 + 8 * by) continue;
+                            sum << (sum.tellp() > 0 ? " + " : "") << "PC(" << pc.src << ", 0x" << std::hex << pc.mask
+                                << std::dec << "u)";
+                        }
+                        if (sum.tellp() <= 0) continue;
+                        s << (first ? "" : " + ") << "((" << sum.str() << ") << " << 8 * by << ")";
+                        first = false;
+                    }
+                } else {
+                    for (size_t i = 0; i < l.size(); ++i) {
+                        const PackPiece& pc = l[i];
+                        s << (i ? " | " : "") << "((r[" << pc.src << "] & 0x" << std::hex << pc.mask << std::dec << "u)";
+                        if (pc.op > 0) s << " << " << pc.op;
+                        if (pc.op < 0) s << " >> " << -pc.op;
+                        s << ")";
+                    }
+                }
+            }
+            s << ")\n";
+        }
+        s << "        break;\n";
+    }
+    s << "    }\n#undef PC\n#undef PUT\n}\n#endif\n";
+    return s.str();
+}
+
+static std::string compact_source_for(const dice_templates* t, Program& prog) {
+    prog.compact = true;
+    derive_layout(t, prog.layout, prog.prog);
+    prog.wpb = 4;
+    // bursts of 5 quads as for the full-bitset tile (3, 4, 5 and 7 measure alike on 14 quads)
+    const std::string src = program_source(t, prog, prog.layout.quads, corpus_in_fast_envelope(t));
+    build_pack_lists(prog, t->n_vocab);
+    return src + pack_source(prog, (t->n_vocab + 63) / 64);
+}
+
+// DICE_PROG_LAYOUT=bits (read at dice_create) keeps the full-bitset tile: fallback and A/B leg.
+static bool compact_wanted() {
+    const char* e = getenv("DICE_PROG_LAYOUT");
+    return !(e && strcmp(e, "bits") == 0);
+}
+
 bool program_wanted(const dice_templates* t) {
     const char* force = getenv("DICE_FORCE_DENSE");
     return !(force && *force == '1') && t->n_templates <= kProgramMaxTemplates;
@@ -589,7 +911,20 @@ bool program_wanted(const dice_templates* t) {
 
 int program_setup(dice_ctx* c, const dice_templates* t) {
     c->kind = 0;
+    c->twq = c->wq;
     if (!program_wanted(t)) return DICE_OK;
+    if (compact_wanted()) {
+        const std::string src = compact_source_for(t, c->prog);
+        int rc = compile_or_load(c, src);
+        if (rc != DICE_OK) return rc;
+        const Program& p = c->prog;
+        if (p.qperm.size() != (size_t)p.layout.quads) return fail(DICE_E_STATE, "program tile permutation size");
+        if (hipModuleGetFunction(&c->prog_pack, c->module, "dice_pack_compact") != hipSuccess)
+            return fail(DICE_E_DEVICE, "hipModuleGetFunction failed");
+        c->twq = p.layout.quads;
+        c->kind = 1;
+        return DICE_OK;
+    }
     const std::string src = source_for(t, c->prog);
     int rc = compile_or_load(c, src);
     if (rc != DICE_OK) return rc;
@@ -601,6 +936,15 @@ int program_setup(dice_ctx* c, const dice_templates* t) {
             return fail(DICE_E_DEVICE, "program tile permutation upload failed");
     }
     c->kind = 1;
+    return DICE_OK;
+}
+
+int program_launch_pack(dice_ctx* c, dice_batch* b, int64_t n, hipStream_t s) {
+    const int64_t n_tiles = (n + 63) / 64;
+    if (n_tiles == 0) return DICE_OK;
+    void* args[] = {&b->d_rows, &n, &b->d_tiles};
+    if (hipModuleLaunchKernel(c->prog_pack, (unsigned)n_tiles, 1, 1, 256, 1, 1, 0, s, args, nullptr) != hipSuccess)
+        return fail(DICE_E_DEVICE, "launch dice_pack_compact failed");
     return DICE_OK;
 }
 
@@ -636,13 +980,47 @@ int program_launch_matrix(dice_ctx* c, dice_batch* b, int32_t k, hipStream_t s) 
 extern "C" int dice_precompile(const dice_templates* t, char* path, int32_t path_cap) {
     if (!t || t->n_templates < 1 || t->n_vocab < 1 || !t->lf_bits) return dice::fail(DICE_E_ARG, "invalid dice_templates");
     if (!dice::program_wanted(t)) return dice::fail(DICE_E_STATE, "corpus uses the dense kernel");
+    // both layouts, so the DICE_PROG_LAYOUT=bits leg finds its code object too; the path
+    // written is the one dice_create will load
+    std::string p[2];
+    for (int compact = 0; compact < 2; ++compact) {
+        dice::Program prog;
+        const std::string src = compact ? dice::compact_source_for(t, prog) : dice::source_for(t, prog);
+        std::vector<char> code;
+        int rc = dice::compile_cached(src, code, &p[compact]);
+        if (rc != DICE_OK) return rc;
+    }
+    if (path && path_cap > 0) snprintf(path, (size_t)path_cap, "%s", p[dice::compact_wanted() ? 1 : 0].c_str());
+    return DICE_OK;
+}
+
+extern "C" int64_t dice_program_source_compact(const dice_templates* t, char* buf, int64_t cap) {
+    if (!t || t->n_templates < 1 || t->n_vocab < 1 || !t->lf_bits || t->n_templates > dice::kProgramMaxTemplates)
+        return -1;
     dice::Program prog;
-    const std::string src = dice::source_for(t, prog);
-    std::vector<char> code;
-    std::string p;
-    int rc = dice::compile_cached(src, code, &p);
-    if (rc == DICE_OK && path && path_cap > 0) snprintf(path, (size_t)path_cap, "%s", p.c_str());
-    return rc;
+    const std::string src = dice::compact_source_for(t, prog);
+    if (buf && cap > 0) {
+        const size_t n = std::min<size_t>((size_t)cap - 1, src.size());
+        memcpy(buf, src.data(), n);
+        buf[n] = 0;
+    }
+    return (int64_t)src.size();
+}
+
+extern "C" int32_t dice_program_layout(const dice_templates* t, int32_t* dest, int32_t* count_base, int32_t* qperm,
+                                       int32_t qperm_cap) {
+    if (!t || t->n_templates < 1 || t->n_vocab < 1 || !t->lf_bits || t->n_templates > dice::kProgramMaxTemplates)
+        return -1;
+    dice::Program prog;
+    (void)dice::compact_source_for(t, prog);
+    const dice::CompactLayout& L = prog.layout;
+    if (dest) memcpy(dest, L.dest.data(), L.dest.size() * sizeof(int32_t));
+    if (count_base) *count_base = 4 * L.bit_dwords;
+    if (qperm) {
+        if (qperm_cap < L.quads) return -1;
+        memcpy(qperm, prog.qperm.data(), (size_t)L.quads * sizeof(int32_t));
+    }
+    return L.quads;
 }
 
 extern "C" int64_t dice_program_source(const dice_templates* t, char* buf, int64_t cap) {
