@@ -281,6 +281,25 @@ int64_t dice_program_source_compact(const dice_templates *templates, char *buf, 
  * quad count, or -1 on bad input or too small a qperm_cap. */
 int32_t dice_program_layout(const dice_templates *templates, int32_t *dest, int32_t *count_base,
                             int32_t *qperm, int32_t qperm_cap);
+/* The tables of the program's matrix-core accumulate stage (DICE_PROG_MATCH),
+ * a pure function of `templates`. The stage scores the compact tile's bit region as a binary matrix
+ * product in K-steps of 64 e2m1 elements (two lane halves of 32). dims[4] receives {K-steps,
+ * 32-template tiles, bit dwords, 1 when dice_create would choose the stage for this corpus by its
+ * cost rule, else 0}. frag (may be NULL) receives the template fragments
+ * [K-step][template tile][lane 32 h + r][4] as dwords: lane (r, h) holds template 32 tile + r,
+ * element e = 8 k + i of half h in nibble i of dword k. map (may be NULL) receives
+ * [K-step][64] int32: for element e of half h (index 32 h + e) the bit of the file's resident
+ * tile row it carries (32 * tile dword + bit, slot order), or -1 for none; the file side holds
+ * such a bit in nibble i of dword k as e2m1 0.5, 1.0, 2.0, 2.0 for k = 0..3. Returns the dword
+ * count of frag, 0 for a corpus the stage cannot take (no bit region, tables too large), or -1
+ * on bad input or too small a capacity (frag_cap dwords, map_cap entries). */
+int64_t dice_program_mfma_tables(const dice_templates *templates, int32_t *dims, uint32_t *frag, int64_t frag_cap,
+                                 int32_t *map, int64_t map_cap);
+
+/* The sparse program's accumulate stage in this ctx: 0 VALU only, 1 matrix cores for batches that
+ * give every CU a 64-file tile (smaller ones take the VALU kernels), 2 matrix cores at every size
+ * (DICE_PROG_MATCH=mfma); -1 for a NULL ctx. */
+int32_t dice_ctx_program_stage(const dice_ctx *ctx);
 
 const char *dice_last_error(void);
 

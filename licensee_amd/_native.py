@@ -30,7 +30,7 @@ EXPORTED_SYMBOLS = (
     'dice_match_confidence', 'dice_batch_match_confidence', 'dice_match_sharded_confidence',
     'dice_batch_scored_pairs', 'dice_vocab_setup', 'dice_batch_upload_text', 'dice_batch_set_rows',
     'dice_batch_download_rows', 'dice_host_alloc', 'dice_host_free',
-    'dice_program_source_compact', 'dice_program_layout',
+    'dice_program_source_compact', 'dice_program_layout', 'dice_program_mfma_tables', 'dice_ctx_program_stage',
 )
 DICE_GATHER_HOST = 0
 DICE_GATHER_DEVICE = 1
@@ -167,6 +167,7 @@ def load_library(path: str = LIB_PATH) -> ctypes.CDLL:
         'dice_destroy': (None, [vp]),
         'dice_ctx_info': (ctypes.c_int, [vp, vp, vp, vp, vp]),
         'dice_ctx_match_kernel': (ctypes.c_int32, [vp]),
+        'dice_ctx_program_stage': (ctypes.c_int32, [vp]),
         'dice_match': (ctypes.c_int, [vp, ctypes.POINTER(_Files), ctypes.c_double, vp, vp, vp]),
         'dice_match_confidence': (ctypes.c_int, [vp, ctypes.POINTER(_Files), ctypes.c_double, vp, vp, vp]),
         'dice_similarity_matrix': (ctypes.c_int, [vp, ctypes.POINTER(_Files), vp, vp, i32, vp, vp]),
@@ -195,6 +196,7 @@ def load_library(path: str = LIB_PATH) -> ctypes.CDLL:
         'dice_program_source': (i64, [ctypes.POINTER(_Templates), ctypes.c_char_p, i64]),
         'dice_program_source_compact': (i64, [ctypes.POINTER(_Templates), ctypes.c_char_p, i64]),
         'dice_program_layout': (i32, [ctypes.POINTER(_Templates), vp, vp, vp, i32]),
+        'dice_program_mfma_tables': (i64, [ctypes.POINTER(_Templates), vp, vp, i64, vp, i64]),
         'dice_exact_setup': (ctypes.c_int, [vp, vp, vp, vp]),
         'dice_batch_exact': (ctypes.c_int, [vp, vp, vp]),
         'dice_batch_download_exact': (ctypes.c_int, [vp, vp, vp]),
@@ -313,6 +315,11 @@ class Scorer:
         """Kernel Dice#match runs on: 0 dense, 1 sparse program, 2 LDS records, 3 postings,
         4 bound-pruned (dice_prune.hip)."""
         return int(load_library().dice_ctx_match_kernel(self._ctx))
+
+    def program_stage(self) -> int:
+        """0: the sparse program accumulates on the VALU; 1: on the matrix cores for large batches;
+        2: on the matrix cores at every size (DICE_PROG_MATCH=mfma)."""
+        return int(load_library().dice_ctx_program_stage(self._ctx))
 
     def match(self, files: FileBatch, threshold: float, confidence: bool = False):
         """(best, overlap, score) per file. confidence=False: score/overlap of the top-ranked

@@ -65,6 +65,7 @@ struct dice_ctx {
     hipFunction_t prog_match = nullptr;
     hipFunction_t prog_matrix = nullptr;    // top-k <= 4
     hipFunction_t prog_matrix16 = nullptr;  // top-k <= 16
+    hipFunction_t prog_match_mfma = nullptr;   // prog_match with the matrix-core accumulate stage (prog.mfma)
     int32_t* d_qperm = nullptr;             // sparse program tile slot -> vocabulary quad (kind 1)
     // Quads per file of the resident tile: wq (the row's quads) except for the sparse program's
     // compact tile, which the generated dice_pack_compact fills (dice_program.cpp).

@@ -19,7 +19,9 @@
 // By default the program runs over the compact tile (derive_layout below):
 // words that belong to exactly the same templates are interchangeable for every overlap, so a
 // large class of them is a byte count (v_and_b32 literal + v_sad_u8) instead of bits, and the
-// file's tile is half as long. DICE_PROG_LAYOUT=bits keeps the full-bitset tile.
+// file's tile is half as long. DICE_PROG_LAYOUT=bits keeps the full-bitset tile. Where it pays
+// (plan_mfma), the module also holds the match kernel with the bit region scored on the matrix
+// cores (kMfmaPrelude); DICE_PROG_MATCH=valu|mfma overrides the rule.
 //
 // The source is compiled with hiprtc for gfx950 and cached by hash under the library
 // directory (lib/cache/dice_prog_<hash>.co), so a corpus compiles once per machine image.
@@ -246,6 +248,107 @@ const char* kMatrixOffer = R"HIP(
     }
 )HIP";
 
+// Matrix-core accumulate stage (device compile only). The bit region of the
+// compact tile against the templates' bit masks is a binary matrix product, files x bits times
+// bits x templates, so v_mfma_scale_f32_32x32x64_f8f6f4 on e2m1 operands computes a 32-template x
+// 32-file block of overlaps per instruction, exactly (every shared bit is 0.5 x 2.0, 1.0 x 1.0 or
+// 2.0 x 0.5 at block scale 2^0; counts < 2^24). Templates are the A operand, pre-widened on the
+// host (dice_mfma_frag, staged in LDS once per workgroup); files are the B operand: lane (r, h)
+// loads whole quads of file 32 m + r -- lane half h takes every other bit quad, a quad's four
+// dwords serve four K-steps -- and widens a dword with 5 VALU (widen_a). Accumulator register g of
+// lane (c, h) is template 32 j + (g & 3) + 8 (g >> 2) + 4 h of file 32 m + c, so one
+// v_permlane32_swap of the m = 0 and m = 1 registers leaves lane l with two templates' overlaps
+// of file l: no LDS transpose. A workgroup of MWK = 12 waves walks a contiguous share of the tiles,
+// wave w taking every MWK-th; the next tile's quads are requested as this tile's K-steps retire
+// them. Match mode only: the matrix kernels, bound by their 600 B per file of stores, measured
+// 17% slower with the stage and keep the VALU program.
+const char* kMfmaPrelude = R"HIP(
+typedef int v8i __attribute__((ext_vector_type(8)));
+typedef float v16f __attribute__((ext_vector_type(16)));
+__device__ __forceinline__ v8i widen_a(u32 v) {
+    v8i r;
+    r[0] = (int)(v & 0x11111111u);
+    r[1] = (int)(v & 0x22222222u);
+    r[2] = (int)(v & 0x44444444u);
+    r[3] = (int)((v >> 1) & 0x44444444u);
+    r[4] = r[5] = r[6] = r[7] = 0;
+    return r;
+}
+__device__ __forceinline__ v8i frag8(uint4 v) {
+    v8i r;
+    r[0] = (int)v.x; r[1] = (int)v.y; r[2] = (int)v.z; r[3] = (int)v.w;
+    r[4] = r[5] = r[6] = r[7] = 0;
+    return r;
+}
+// FP4 x FP4 (cbsz = blgp = 4), block scales 2^0 (E8M0 0x7F in every byte). The scales must be
+// VGPRs: given a constant, the runtime compiler folds it into an SGPR operand, which the
+// instruction does not take (every product then came out as +inf), so ms_ is made opaque (MFMA_HEAD).
+// Observed with hiprtc of ROCm 7.2 (HIP 7.2.26015, AMD clang 22.0.0git roc-7.2.0); the same release's
+// offline compiler uses a VGPR. Like ll_ in MFMA_TILE, which keeps the fragment reads inside the tile
+// loop, it guards against one compiler's folding and hoisting: tests/test_gpu_prog_mfma.py fails on
+// every file with a bit set if either stops working.
+#define MFMA44(a, b, c) __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(a, b, c, 4, 4, 0, ms_, 0, ms_)
+// acc[TA] += overlaps of template TA, acc[TB] += of template TB (rows g and g + 4 of the block),
+// lane = file: lanes 32-63 of the m = 0 register swap with lanes 0-31 of the m = 1 register
+#define MFMA_FOLD2(C0, C1, G, TA, TB) { typedef u32 u32x2_ __attribute__((ext_vector_type(2))); \
+    const u32x2_ r_ = __builtin_amdgcn_permlane32_swap((u32)C0[G], (u32)C1[G], false, false); \
+    acc[TA] += r_[0]; acc[TB] += r_[1]; }
+#define MFMA_FOLD1(C0, C1, G, TA) { typedef u32 u32x2_ __attribute__((ext_vector_type(2))); \
+    const u32x2_ r_ = __builtin_amdgcn_permlane32_swap((u32)C0[G], (u32)C1[G], false, false); \
+    acc[TA] += r_[0]; }
+// Workgroup head: template fragments into LDS, the workgroup's share of the tiles, the wave's first
+// tile and its quads
+#define MFMA_HEAD \
+    __shared__ uint4 tfrag[MFMA_FRAGS * 64]; \
+    for (int i = threadIdx.x; i < MFMA_FRAGS * 64; i += 64 * MWK) tfrag[i] = ((const uint4*)dice_mfma_frag)[i]; \
+    __syncthreads(); \
+    const int lane = threadIdx.x & 63; \
+    int ms_ = 0x7F7F7F7F; asm volatile("" : "+v"(ms_)); \
+    const i64 nt_ = (n + 63) >> 6; \
+    const i64 t1 = nt_ * (i64)(blockIdx.x + 1) / (i64)gridDim.x; \
+    i64 tile = nt_ * (i64)blockIdx.x / (i64)gridDim.x + __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)); \
+    if (tile >= t1) return; \
+    MFMA_QDECL \
+    { const uint4* nq_ = files + tile * (i64)(WQ * 64) + (lane & 31); MFMA_QLOAD }
+// Per tile: the quads of the wave's next tile (this one again after the last: loaded, never used)
+#define MFMA_TILE \
+    const i64 file = tile * 64 + lane; \
+    const uint4* fp = files + tile * (i64)(WQ * 64) + lane; \
+    const uint4* nq_ = files + (tile + MWK < t1 ? tile + MWK : tile) * (i64)(WQ * 64) + (lane & 31); \
+    int ll_ = lane; asm volatile("" : "+v"(ll_));   /* fragment reads stay in the loop (and out of scratch) */
+)HIP";
+
+const char* kMatchKernelMfma = R"HIP(
+extern "C" __global__ __launch_bounds__(64 * MWK) void dice_prog_match_mfma(
+    const uint4* __restrict__ files, i64 n, const u32* __restrict__ wfp, const i32* __restrict__ lenp,
+    const unsigned char* __restrict__ ccp, double thr, i32* __restrict__ best_out,
+    u32* __restrict__ ov_out, double* __restrict__ score_out) {
+    MFMA_HEAD
+    for (; tile < t1; tile += MWK) {
+        MFMA_TILE
+        const u32 wf = wfp[file];
+        const i32 lf = lenp[file];
+        const bool cc = ccp[file] != 0;
+        FILE_PROLOGUE_MFMA
+        const bool fast = CORPUS_FAST && wf < (1u << 20) && lf >= 0 && lf < (1 << 21);
+        u32 bo = 0xFF000000u; i32 bd = 1;
+        if (__all(fast)) {
+            MATCH_BODY(true)
+        } else {
+            MATCH_BODY(false)
+        }
+        if (file < n) {
+            const i32 bi = (bo >> 24) == 0xFFu ? -1 : (i32)(bo >> 24);
+            const u32 bov = bo & 0xFFFFFFu;
+            const double s = bi >= 0 ? sc(bov, bd) : 0.0;
+            MSTORE(best_out + file, (bi >= 0 && s >= thr) ? bi : -1);
+            MSTORE(ov_out + file, bov);
+            MSTORE(score_out + file, s);
+        }
+    }
+}
+)HIP";
+
 uint64_t fnv1a(const std::string& s) {
     uint64_t h = 1469598103934665603ULL;
     for (unsigned char c : s) {
@@ -381,6 +484,65 @@ static void emit_macro(std::ostringstream& s, const std::string& head, const std
     s << "\n";
 }
 
+// Cost rule of the matrix-core stage: it runs when the VALU instructions of the bit entries exceed
+// kMfmaPayRatio times the stage's own cost in the same unit (one VALU issue = 4 cycles: widening 5
+// per fragment, ~3 per template to fold, matrix cycles / 4). One measured point: the vendored corpus,
+// ratio 2.02, gains 1.21x. The constant sits halfway between break-even on
+// paper and that point; it is not calibrated on a second corpus.
+constexpr double kMfmaPayRatio = 1.5;
+constexpr int kMfmaMatchWaves = 12;   // MWK of the generated kernel
+constexpr int64_t kMfmaMaxFragBytes = 96 * 1024;   // one 12-wave workgroup per CU: 3 waves per SIMD
+
+// Shape and costs of the stage for the layout in p (no slot order needed).
+static void plan_mfma(const dice_templates* t, Program& p) {
+    MfmaTables& m = p.mf;
+    const CompactLayout& L = p.layout;
+    const int32_t qb = (L.bit_dwords + 3) / 4, np = (qb + 1) / 2;
+    m.ksteps = 4 * np;
+    m.ntiles = (t->n_templates + 31) / 32;
+    m.valu_cost = 0;
+    for (const Entry& e : p.prog)
+        if (!e.sum) m.valu_cost += e.mask == 0xFFFFFFFFu ? 1 : 2;
+    m.stage_cost = 2 * 5 * (int64_t)m.ksteps + 3 * (int64_t)t->n_templates + (int64_t)m.ksteps * m.ntiles * 2 * 32 / 4;
+    m.eligible = L.bit_dwords > 0 && (int64_t)m.ksteps * m.ntiles * 1024 <= kMfmaMaxFragBytes;
+    m.pays = m.eligible && (double)m.valu_cost > kMfmaPayRatio * (double)m.stage_cost;
+}
+
+// Fragment table and file-side map, once p.qperm is known.
+static void build_mfma_tables(const dice_templates* t, Program& p) {
+    MfmaTables& m = p.mf;
+    const CompactLayout& L = p.layout;
+    const int32_t T = t->n_templates, qb = (L.bit_dwords + 3) / 4, np = m.ksteps / 4;
+    std::vector<int32_t> slot_of((size_t)L.quads, 0);
+    for (size_t s = 0; s < p.qperm.size(); ++s) slot_of[(size_t)p.qperm[s]] = (int32_t)s;
+    m.slots.assign((size_t)2 * np, -1);
+    for (int32_t q = 0; q < qb; ++q) m.slots[(size_t)q] = slot_of[(size_t)q];
+    std::vector<uint32_t> mask((size_t)T * std::max(1, L.bit_dwords), 0u);
+    for (const Entry& e : p.prog)
+        if (!e.sum) mask[(size_t)e.tpl * L.bit_dwords + e.dword] = e.mask;
+    m.frag.assign((size_t)m.ksteps * m.ntiles * 64 * 4, 0u);
+    m.map.assign((size_t)m.ksteps * 64, -1);
+    for (int32_t s = 0; s < m.ksteps; ++s) {
+        for (int32_t h = 0; h < 2; ++h) {
+            const int32_t q = 2 * (s / 4) + h, dw = 4 * q + s % 4;
+            if (q >= qb || dw >= L.bit_dwords) continue;
+            const int32_t tile_dword = 4 * m.slots[(size_t)q] + s % 4;
+            for (int32_t e = 0; e < 32; ++e) {   // element e = 8 k + i: nibble i of fragment dword k, bit 4 i + k
+                const int32_t bit = 4 * (e % 8) + e / 8;
+                if (32 * dw + bit < L.n_bits) m.map[(size_t)s * 64 + 32 * h + e] = 32 * tile_dword + bit;
+            }
+            for (int32_t tp = 0; tp < T; ++tp) {
+                const uint32_t v = mask[(size_t)tp * L.bit_dwords + dw];
+                uint32_t* f = &m.frag[(((size_t)s * m.ntiles + tp / 32) * 64 + 32 * h + tp % 32) * 4];
+                f[0] = (v << 2) & 0x44444444u;   // the values paired with widen_a's: 2.0, 1.0, 0.5, 0.5
+                f[1] = v & 0x22222222u;
+                f[2] = (v >> 2) & 0x11111111u;
+                f[3] = (v >> 3) & 0x11111111u;
+            }
+        }
+    }
+}
+
 // Program order: dword-major -- every template accumulator stays live (acc[NT]); file quads are
 // loaded in bursts right before they are consumed, so a file dword's live range is a few
 // instructions; the epilogue (denominator, compare) runs once per template after the last quad.
@@ -422,7 +584,7 @@ std::string program_source(const dice_templates* t, Program& p, int32_t wq, bool
         o << "{ if ((!FASTV && (bo >> 24) == 0xFFu) || ge<FASTV>(a, d, bo, bd)) { bo = a; bd = d; } }";
         return o.str();
     };
-    std::ostringstream match_body, matrix_body, prologue;
+    std::ostringstream match_body, matrix_body, prologue, mfma_pro, mfma_defs;
     {
         std::vector<Entry> dm(p.prog);
         std::stable_sort(dm.begin(), dm.end(), [](const Entry& x, const Entry& y) {
@@ -514,6 +676,65 @@ std::string program_source(const dice_templates* t, Program& p, int32_t wq, bool
             group_loads(prologue, 0, 0);
             stream(prologue);
         }
+        if (p.compact && p.mf.eligible) build_mfma_tables(t, p);
+        if (p.mfma) {
+            // the matrix-core form of the prologue (kMfmaPrelude): count quads requested lane per
+            // file, the K-steps pair by pair of bit quads with the next tile's pair requested
+            // behind them, the fold into acc[], then the count entries as in the VALU program
+            const MfmaTables& m = p.mf;
+            const int32_t np = m.ksteps / 4, nj = m.ntiles, T = t->n_templates;
+            std::ostringstream& o = mfma_pro;
+            o << "u32 acc[NT];\n_Pragma(\"unroll\") for (int i = 0; i < NT; ++i) acc[i] = ACC_INIT(i);\n";
+            std::vector<std::pair<size_t, size_t>> crange(quads.size(), {0, 0});   // count entries per slot
+            for (size_t i = 0; i < quads.size(); ++i) {
+                size_t b = range[i].first;
+                while (b < range[i].second && !dm[b].sum) ++b;
+                crange[i] = {b, range[i].second};
+                if (b < range[i].second) o << "const uint4 cq_" << i << " = ldq(fp + " << quads[i] * 64 << ");\n";
+            }
+            for (int32_t j = 0; j < nj; ++j) o << "v16f c" << j << "_0 = {}, c" << j << "_1 = {};\n";
+            const char* comp = "xyzw";
+            for (int32_t u = 0; u < np; ++u) {
+                for (int32_t d = 0; d < 4; ++d) {
+                    const int32_t s = 4 * u + d;
+                    bool any = false;
+                    for (int32_t e = 0; e < 64; ++e) any = any || m.map[(size_t)s * 64 + e] >= 0;
+                    if (!any) continue;
+                    o << "{ const v8i b0_ = widen_a(q0_" << u << "." << comp[d] << "), b1_ = widen_a(q1_" << u << "."
+                      << comp[d] << ");\n";
+                    for (int32_t j = 0; j < nj; ++j)
+                        o << "{ const v8i a_ = frag8(tfrag[" << (s * nj + j) * 64 << " + ll_]); c" << j << "_0 = MFMA44(a_, b0_, c"
+                          << j << "_0); c" << j << "_1 = MFMA44(a_, b1_, c" << j << "_1); }\n";
+                    o << "}\n";
+                }
+                o << "q0_" << u << " = ldq(nq_ + o_" << u << "); q1_" << u << " = ldq(nq_ + o_" << u << " + 32);\n";
+            }
+            for (int32_t j = 0; j < nj; ++j)
+                for (int32_t g = 0; g < 16; ++g) {
+                    const int32_t ta = 32 * j + (g & 3) + 8 * (g >> 2), tb = ta + 4;
+                    if (ta >= T) continue;
+                    if (tb < T)
+                        o << "MFMA_FOLD2(c" << j << "_0, c" << j << "_1, " << g << ", " << ta << ", " << tb << ")\n";
+                    else
+                        o << "MFMA_FOLD1(c" << j << "_0, c" << j << "_1, " << g << ", " << ta << ")\n";
+                }
+            for (size_t i = 0; i < quads.size(); ++i) {
+                if (crange[i].first == crange[i].second) continue;
+                o << "{ const u32 f[4] = {cq_" << i << ".x, cq_" << i << ".y, cq_" << i << ".z, cq_" << i << ".w};\n";
+                o << acc_quad(dm, crange[i].first, crange[i].second, quads[i]);
+                o << "}\n";
+            }
+            // per-lane quad offsets (lane half h takes the odd quad of each pair), declarations, loads
+            std::ostringstream qd, ql;
+            for (int32_t u = 0; u < np; ++u) {
+                const int32_t s0 = m.slots[(size_t)2 * u], s1 = m.slots[(size_t)2 * u + 1] >= 0 ? m.slots[(size_t)2 * u + 1] : s0;
+                qd << "const int o_" << u << " = (lane >> 5) ? " << s1 * 64 << " : " << s0 * 64 << "; uint4 q0_" << u
+                   << ", q1_" << u << ";\n";
+                ql << "q0_" << u << " = ldq(nq_ + o_" << u << "); q1_" << u << " = ldq(nq_ + o_" << u << " + 32);\n";
+            }
+            emit_macro(mfma_defs, "MFMA_QDECL", qd.str());
+            emit_macro(mfma_defs, "MFMA_QLOAD", ql.str());
+        }
         for (int32_t i = 0; i < t->n_templates; ++i) {
             match_body << "{ const u32 a = acc[" << i << "]; i32 d; " << den[i] << offer(i) << " }\n";
             matrix_body << "{ const u32 a = acc[" << i << "]; i32 d; " << den[i] << "MOFFER(" << i << ", "
@@ -536,6 +757,16 @@ std::string program_source(const dice_templates* t, Program& p, int32_t wq, bool
     for (int km : {4, 16}) {
         s << "#define KM " << km << "\n#define KNAME dice_prog_matrix" << km << "\n" << kMatrixKernel
           << "#undef KM\n#undef KNAME\n";
+    }
+    if (p.mfma) {
+        // the match kernel with the matrix-core accumulate stage, device compile only
+        s << "#ifdef __HIP_DEVICE_COMPILE__\n#define MFMA_FRAGS " << p.mf.ksteps * p.mf.ntiles << "\n";
+        s << "__device__ const u32 dice_mfma_frag[" << p.mf.frag.size() << "] __attribute__((aligned(16))) = {\n" << std::hex;
+        for (size_t i = 0; i < p.mf.frag.size(); ++i) s << "0x" << p.mf.frag[i] << (i % 16 == 15 ? ",\n" : ",");
+        s << std::dec << "};\n" << kMfmaPrelude << mfma_defs.str();
+        emit_macro(s, "FILE_PROLOGUE_MFMA", mfma_pro.str());
+        s << "#define MWK " << kMfmaMatchWaves << "\n#undef ACC_INIT\n#define ACC_INIT(i) ((u32)(i) << 24)\n" << kMatchKernelMfma
+          << "#undef ACC_INIT\n#define ACC_INIT(i) 0u\n#endif\n";
     }
     return s.str();
 }
@@ -586,7 +817,22 @@ static int compile_or_load(dice_ctx* c, const std::string& src) {
         hipModuleGetFunction(&c->prog_matrix, c->module, "dice_prog_matrix4") != hipSuccess ||
         hipModuleGetFunction(&c->prog_matrix16, c->module, "dice_prog_matrix16") != hipSuccess)
         return fail(DICE_E_DEVICE, "hipModuleGetFunction failed");
+    if (c->prog.mfma) {
+        if (hipModuleGetFunction(&c->prog_match_mfma, c->module, "dice_prog_match_mfma") != hipSuccess)
+            return fail(DICE_E_DEVICE, "hipModuleGetFunction failed");
+        if (hipDeviceGetAttribute(&c->n_cu, hipDeviceAttributeMultiprocessorCount, c->device) != hipSuccess || c->n_cu < 1)
+            c->n_cu = 256;
+    }
     return DICE_OK;
+}
+
+// The matrix-core kernels take a launch when the module has them and the batch gives every CU a
+// tile (below that the fragment fill per workgroup outweighs the stage; DICE_PROG_MATCH=mfma
+// takes them at every size). One workgroup per CU at most, never more than there are tiles.
+static bool mfma_launch(const dice_ctx* c, int64_t n_tiles, unsigned* grid) {
+    if (!c->prog.mfma || !(c->prog.mfma_forced || n_tiles >= c->n_cu)) return false;
+    *grid = (unsigned)std::min<int64_t>(n_tiles, c->n_cu);
+    return true;
 }
 
 static bool corpus_in_fast_envelope(const dice_templates* t) {
@@ -892,6 +1138,12 @@ static std::string compact_source_for(const dice_templates* t, Program& prog) {
     prog.compact = true;
     derive_layout(t, prog.layout, prog.prog);
     prog.wpb = 4;
+    // DICE_PROG_MATCH (read at dice_create): `mfma` takes the matrix-core stage wherever it is
+    // eligible, `valu` never; by default the cost rule decides
+    plan_mfma(t, prog);
+    const char* pm = getenv("DICE_PROG_MATCH");
+    prog.mfma_forced = pm && strcmp(pm, "mfma") == 0 && prog.mf.eligible;
+    prog.mfma = prog.mfma_forced || (!(pm && strcmp(pm, "valu") == 0) && prog.mf.pays);
     // bursts of 5 quads as for the full-bitset tile (3, 4, 5 and 7 measure alike on 14 quads)
     const std::string src = program_source(t, prog, prog.layout.quads, corpus_in_fast_envelope(t));
     build_pack_lists(prog, t->n_vocab);
@@ -951,11 +1203,15 @@ int program_launch_pack(dice_ctx* c, dice_batch* b, int64_t n, hipStream_t s) {
 int program_launch_match(dice_ctx* c, dice_batch* b, double thr, hipStream_t s) {
     const int64_t n_tiles = (b->n + 63) / 64;
     const int32_t wpb = c->prog.wpb;
-    const unsigned grid = (unsigned)((n_tiles + wpb - 1) / wpb);
+    unsigned grid = (unsigned)((n_tiles + wpb - 1) / wpb), threads = 64 * wpb;
     hipFunction_t fn = c->prog_match;
+    if (mfma_launch(c, n_tiles, &grid)) {
+        fn = c->prog_match_mfma;
+        threads = 64 * kMfmaMatchWaves;
+    }
     int64_t n = b->n;
     void* args[] = {&b->d_tiles, &n, &b->d_wf, &b->d_len, &b->d_cc, &thr, &b->d_best, &b->d_ov, &b->d_score};
-    if (hipModuleLaunchKernel(fn, grid, 1, 1, 64 * wpb, 1, 1, 0, s, args, nullptr) != hipSuccess)
+    if (hipModuleLaunchKernel(fn, grid, 1, 1, threads, 1, 1, 0, s, args, nullptr) != hipSuccess)
         return fail(DICE_E_DEVICE, "launch dice_prog_match failed");
     return DICE_OK;
 }
@@ -1021,6 +1277,36 @@ extern "C" int32_t dice_program_layout(const dice_templates* t, int32_t* dest, i
         memcpy(qperm, prog.qperm.data(), (size_t)L.quads * sizeof(int32_t));
     }
     return L.quads;
+}
+
+extern "C" int32_t dice_ctx_program_stage(const dice_ctx* ctx) {
+    if (!ctx) return -1;
+    return ctx->kind == 1 && ctx->prog.mfma ? (ctx->prog.mfma_forced ? 2 : 1) : 0;
+}
+
+extern "C" int64_t dice_program_mfma_tables(const dice_templates* t, int32_t* dims, uint32_t* frag, int64_t frag_cap,
+                                            int32_t* map, int64_t map_cap) {
+    if (!t || t->n_templates < 1 || t->n_vocab < 1 || !t->lf_bits || t->n_templates > dice::kProgramMaxTemplates)
+        return -1;
+    dice::Program prog;
+    (void)dice::compact_source_for(t, prog);
+    const dice::MfmaTables& m = prog.mf;
+    if (dims) {
+        dims[0] = m.ksteps;
+        dims[1] = m.ntiles;
+        dims[2] = prog.layout.bit_dwords;
+        dims[3] = m.pays ? 1 : 0;
+    }
+    if (!m.eligible) return 0;
+    if (frag) {
+        if (frag_cap < (int64_t)m.frag.size()) return -1;
+        memcpy(frag, m.frag.data(), m.frag.size() * sizeof(uint32_t));
+    }
+    if (map) {
+        if (map_cap < (int64_t)m.map.size()) return -1;
+        memcpy(map, m.map.data(), m.map.size() * sizeof(int32_t));
+    }
+    return (int64_t)m.frag.size();
 }
 
 extern "C" int64_t dice_program_source(const dice_templates* t, char* buf, int64_t cap) {

@@ -43,7 +43,25 @@ struct PackPiece {
     int32_t op;
 };
 
+// Tables of the matrix-core accumulate stage over the compact tile's bit region (dice_program.cpp,
+// "Matrix-core accumulate stage"). K-step s takes, per lane half h, one tile dword: dword s % 4 of
+// the quad in slot slots[2 (s / 4) + h] (-1: none, the template elements are zero).
+struct MfmaTables {
+    int32_t ksteps = 0;               // K-steps of 64 elements (4 per pair of bit quads)
+    int32_t ntiles = 0;               // 32-template tiles
+    std::vector<int32_t> slots;       // [ksteps / 2] tile slot of the quad each lane half loads (-1: padding)
+    std::vector<uint32_t> frag;       // [ksteps][ntiles][64][4] pre-widened template fragments
+    std::vector<int32_t> map;         // [ksteps][64] tile bit carried by element e of half h (at 32 h + e), or -1
+    int64_t valu_cost = 0;            // VALU instructions of the bit entries the stage replaces
+    int64_t stage_cost = 0;           // the stage in VALU-issue units: fixed VALU + matrix cycles / 4
+    bool eligible = false;            // a bit region, and the fragments fit in LDS at >= 2 waves per SIMD
+    bool pays = false;                // cost rule (kMfmaPayRatio)
+};
+
 struct Program {
+    bool mfma = false;                // the module also holds dice_prog_match_mfma
+    bool mfma_forced = false;         // DICE_PROG_MATCH=mfma: small batches take them too
+    MfmaTables mf;
     std::vector<Entry> prog;          // sorted by (dword, tpl)
     std::vector<int32_t> dword_map;   // vocab dword -> file dword in the remapped layout (-1: unused)
     int32_t wpb = 4;                  // waves (64-file tiles) per workgroup
