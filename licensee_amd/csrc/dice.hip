@@ -444,6 +444,7 @@ int dice_create(const dice_templates* t, int32_t device, dice_ctx** out) {
     dice_ctx* c = new (std::nothrow) dice_ctx();
     if (!c) return fail(DICE_E_NOMEM, "ctx alloc");
     c->device = device;
+    c->n_cu = prop.multiProcessorCount < 1 ? 256 : prop.multiProcessorCount;
     c->T = t->n_templates;
     c->V = t->n_vocab;
     c->w64 = dice_words64(t->n_vocab);
@@ -515,7 +516,7 @@ int dice_ctx_info(const dice_ctx* ctx, int32_t* T, int32_t* V, int32_t* kind, in
     if (kind) *kind = ctx->kind;
     if (entries)
         *entries = ctx->kind == 2 ? (int32_t)ctx->lds_entries
-                 : ctx->kind == 3 ? (int32_t)ctx->post_rows : (int32_t)ctx->prog.entries();
+                 : ctx->kind == 3 ? (int32_t)ctx->post_rows : (int32_t)ctx->prog.prog.size();
     return DICE_OK;
 }
 

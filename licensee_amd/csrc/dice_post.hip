@@ -943,8 +943,6 @@ int post_setup(dice_ctx* c, const dice_templates* t) {
     // file's (another wave's) -- partial-line writes cost read-modify-write traffic in HBM
     c->post_ld = (T + 31) / 32 * 32;
     c->post_rows = nlong;
-    if (hipDeviceGetAttribute(&c->n_cu, hipDeviceAttributeMultiprocessorCount, c->device) != hipSuccess || c->n_cu < 1)
-        c->n_cu = 256;
     c->kind = 3;
     return DICE_OK;
 }

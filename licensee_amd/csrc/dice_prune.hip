@@ -654,8 +654,6 @@ int prune_setup(dice_ctx* c, const dice_templates* t) {
     for (int32_t i = 0; i < T; ++i) c->prune_max_lf = std::max<uint32_t>(c->prune_max_lf, t->lf_size[i]);
     const char* lr = getenv("DICE_PRUNE_LONG_ROUTE");
     c->prune_long_route = lr && *lr ? std::max(0, atoi(lr)) : 4;
-    if (hipDeviceGetAttribute(&c->n_cu, hipDeviceAttributeMultiprocessorCount, c->device) != hipSuccess || c->n_cu < 1)
-        c->n_cu = 256;
     c->prune = true;
     return DICE_OK;
 }

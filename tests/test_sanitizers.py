@@ -94,3 +94,63 @@ def test_host_library_under_asan_ubsan(tmp_path, march):
     assert r.returncode == 0, r.stderr[-4000:]
     assert r.stdout.startswith('ok '), r.stdout
     assert 'runtime error' not in r.stderr and 'AddressSanitizer' not in r.stderr, r.stderr[-4000:]
+
+
+# The sparse program's generator (csrc/dice_program_gen.cpp) under the same sanitizers:
+# tests/sanitize/program_driver.cpp plans and emits the program for the full-bitset tile and for the
+# compact tile with the VALU and the matrix-core match stage. The corpora are the shapes at which
+# its index code can go wrong; every text must be what the shared library returns.
+
+@pytest.fixture(scope='module')
+def program_driver(tmp_path_factory):
+    exe = str(tmp_path_factory.mktemp('progdrv') / 'drv')
+    csrc = os.path.join(ROOT, 'licensee_amd', 'csrc')
+    subprocess.run(['g++', '-std=c++17', '-O1', '-g', '-fno-omit-frame-pointer', '-fsanitize=address,undefined',
+                    '-fno-sanitize-recover=all', '-I', csrc, '-o', exe, os.path.join(HERE, 'sanitize', 'program_driver.cpp'),
+                    os.path.join(csrc, 'dice_program_gen.cpp')], check=True)
+    return exe
+
+
+def _program_corpus(name):
+    from licensee_amd.corpus import TemplateCorpus
+    from licensee_amd.license import License
+    from tests.helpers import ArrayCorpus
+    from tests.test_gpu_corpus_sizes import corpus_of
+    if name == 'vendored':
+        return TemplateCorpus(License.all(hidden=True, pseudo=False))
+    if name == 'nofields':   # test_corpus_without_count_fields: no count fields, V no multiple of 64
+        T, V = 8, 255
+        member = ((np.arange(1, V + 1)[None, :] >> np.arange(T)[:, None]) & 1).astype(np.uint8)
+        pad = np.zeros((T, 256), np.uint8)
+        pad[:, :V] = member
+        size = member.sum(1).astype(np.uint32)
+        return ArrayCorpus(np.packbits(pad, axis=1, bitorder='little').view(np.uint64), size, np.ones(T, np.uint32),
+                           np.full(T, 5, np.int32), (size * 6).astype(np.int32), np.zeros(T, np.uint8), V)
+    # 1: no bit region; 33: two 32-template tiles, the second nearly empty; 64: the most the program serves
+    return TemplateCorpus(corpus_of(int(name)))
+
+
+@pytest.mark.skipif(shutil.which('g++') is None, reason='needs g++')
+@pytest.mark.parametrize('name', ['vendored', '1', '33', '64', 'nofields'])
+def test_program_generator_under_asan_ubsan(tmp_path, monkeypatch, program_driver, name):
+    from tests.test_program_codegen import generated_source
+    from tests.test_program_compact_codegen import compact_source
+    c = _program_corpus(name)
+    T = len(c.lf_size)
+    arrays = [(c.lf_bits, np.uint64), (c.lf_size, np.uint32), (c.fields_set_size, np.uint32),
+              (c.length_slack, np.int32), (c.length, np.int32), (c.is_cc, np.uint8)]
+    inp = tmp_path / 'templates.bin'
+    inp.write_bytes(struct.pack('<ii', T, c.n_vocab) +
+                    b''.join(np.ascontiguousarray(a, dtype=dt).tobytes() for a, dt in arrays))
+    env = dict(os.environ, ASAN_OPTIONS='detect_leaks=1:abort_on_error=1', UBSAN_OPTIONS='print_stacktrace=1')
+    r = subprocess.run([program_driver, str(inp), str(tmp_path / 'prog')], capture_output=True, text=True, env=env,
+                       timeout=300)
+    assert r.returncode == 0, r.stderr[-4000:]
+    assert r.stdout.startswith('ok '), r.stdout
+    assert r.stderr == '', r.stderr[-4000:]
+    monkeypatch.delenv('DICE_PROG_DIAG', raising=False)
+    monkeypatch.delenv('DICE_PROG_LAYOUT', raising=False)
+    assert (tmp_path / 'prog.bits').read_bytes() == generated_source(c).encode()
+    for match in ('valu', 'mfma'):
+        monkeypatch.setenv('DICE_PROG_MATCH', match)
+        assert (tmp_path / f'prog.{match}').read_bytes() == compact_source(c).encode()
