@@ -295,6 +295,17 @@ int32_t dice_program_layout(const dice_templates *templates, int32_t *dest, int3
  * on bad input or too small a capacity (frag_cap dwords, map_cap entries). */
 int64_t dice_program_mfma_tables(const dice_templates *templates, int32_t *dims, uint32_t *frag, int64_t frag_cap,
                                  int32_t *map, int64_t map_cap);
+/* How the device holds those tables, a pure function of `templates`. The kernel keeps the templates
+ * in two blocks of 32 rows, chosen so that, with the bit region grouped as [words of block 0 only |
+ * of both | of block 1 only] (dice_program_layout's dest follows that order), as few (K-step, block)
+ * fragments as possible have a non-zero element; it reads and multiplies only those. rows[64] (may be
+ * NULL) receives the template in device row 32 block + r, or -1 for a padded row; every template
+ * appears once, and a corpus of at most 32 templates keeps row i = template i. live (may be NULL)
+ * receives one byte per [K-step][block] (dims[0] * dims[1] of dice_program_mfma_tables): 1 iff the
+ * fragment of the canonical table, its rows gathered through rows[], has a non-zero element. Returns
+ * the number of live fragments, 0 for a corpus the stage cannot take, or -1 on bad input or too small
+ * a live_cap (bytes). */
+int32_t dice_program_mfma_rows(const dice_templates *templates, int32_t *rows, uint8_t *live, int64_t live_cap);
 
 /* The sparse program's accumulate stage in this ctx: 0 VALU only, 1 matrix cores for batches that
  * give every CU a 64-file tile (smaller ones take the VALU kernels), 2 matrix cores at every size

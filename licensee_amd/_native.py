@@ -31,6 +31,7 @@ EXPORTED_SYMBOLS = (
     'dice_batch_scored_pairs', 'dice_vocab_setup', 'dice_batch_upload_text', 'dice_batch_set_rows',
     'dice_batch_download_rows', 'dice_host_alloc', 'dice_host_free',
     'dice_program_source_compact', 'dice_program_layout', 'dice_program_mfma_tables', 'dice_ctx_program_stage',
+    'dice_program_mfma_rows',
 )
 DICE_GATHER_HOST = 0
 DICE_GATHER_DEVICE = 1
@@ -197,6 +198,7 @@ def load_library(path: str = LIB_PATH) -> ctypes.CDLL:
         'dice_program_source_compact': (i64, [ctypes.POINTER(_Templates), ctypes.c_char_p, i64]),
         'dice_program_layout': (i32, [ctypes.POINTER(_Templates), vp, vp, vp, i32]),
         'dice_program_mfma_tables': (i64, [ctypes.POINTER(_Templates), vp, vp, i64, vp, i64]),
+        'dice_program_mfma_rows': (i32, [ctypes.POINTER(_Templates), vp, vp, i64]),
         'dice_exact_setup': (ctypes.c_int, [vp, vp, vp, vp]),
         'dice_batch_exact': (ctypes.c_int, [vp, vp, vp]),
         'dice_batch_download_exact': (ctypes.c_int, [vp, vp, vp]),

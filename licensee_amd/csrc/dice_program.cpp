@@ -79,6 +79,7 @@ static ProgramOptions program_options_from_env() {
     o.diag = is(diag, "noacc")    ? ProgramOptions::kNoAcc
              : is(diag, "noepi")  ? ProgramOptions::kNoEpi
              : is(diag, "timing") ? ProgramOptions::kTiming
+             : is(diag, "nomfma") ? ProgramOptions::kNoMfma
                                   : ProgramOptions::kNone;
     return o;
 }
@@ -291,4 +292,19 @@ extern "C" int64_t dice_program_mfma_tables(const dice_templates* t, int32_t* di
         memcpy(map, m.map.data(), m.map.size() * sizeof(int32_t));
     }
     return (int64_t)m.frag.size();
+}
+
+extern "C" int32_t dice_program_mfma_rows(const dice_templates* t, int32_t* rows, uint8_t* live, int64_t live_cap) {
+    if (!templates_ok(t)) return -1;
+    const dice::Program prog = plan_from_env(t, true);
+    const dice::MfmaTables& m = prog.mf;
+    if (!m.eligible) return 0;
+    if (rows) {
+        for (int i = 0; i < 64; ++i) rows[i] = i < (int)m.rows.size() ? m.rows[(size_t)i] : -1;
+    }
+    if (live) {
+        if (live_cap < (int64_t)m.live.size()) return -1;
+        memcpy(live, m.live.data(), m.live.size());
+    }
+    return m.n_live;
 }

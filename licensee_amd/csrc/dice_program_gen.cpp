@@ -23,8 +23,9 @@
 // pays (plan_mfma), the module also holds the match kernel with the bit region scored on the matrix
 // cores (kMfmaPrelude); ProgramOptions::match overrides the rule.
 //
-// Two stages: plan_program (layout -> entries -> schedule -> matrix-core tables -> pack lists, no
-// text) and emit_program (text from the plan, nothing else).
+// Two stages: plan_program (layout -> matrix-core shape, row assignment and word grouping -> entries
+// -> schedule -> matrix-core tables and cost rule -> pack lists, no text) and emit_program (text from
+// the plan, nothing else).
 #include "dice_program_gen.h"
 
 #include <algorithm>
@@ -148,10 +149,9 @@ int entry_cost(const Entry& e) { return e.mask == 0xFFFFFFFFu ? 1 : 2; }
 
 // Layout for the corpus and its entries: the class-size threshold that gives the fewest tile quads,
 // on a tie the fewest program instructions (then the smallest threshold). A class of <= 8 words
-// never takes more bits as bits than as a count byte, so thresholds start at 8.
-void derive_layout(const dice_templates* t, CompactLayout& best, std::vector<Entry>& entries) {
+// never takes more bits as bits than as a count byte, so thresholds start at 8. `col` is word_columns(t).
+void derive_layout(const dice_templates* t, const std::vector<uint64_t>& col, CompactLayout& best, std::vector<Entry>& entries) {
     const int32_t V = t->n_vocab;
-    const std::vector<uint64_t> col = word_columns(t);
     std::vector<WordClass> classes;
     {
         std::vector<int32_t> order;
@@ -238,23 +238,193 @@ Schedule build_schedule(const std::vector<Entry>& entries, int32_t wq) {
 
 // Cost rule of the matrix-core stage: it runs when the VALU instructions of the bit entries exceed
 // kMfmaPayRatio times the stage's own cost in the same unit (one VALU issue = 4 cycles: widening 5
-// per fragment, ~3 per template to fold, matrix cycles / 4). One measured point: the vendored corpus,
-// ratio 2.02, gains 1.21x. The constant sits halfway between break-even on
-// paper and that point; it is not calibrated on a second corpus.
+// per fragment, ~3 per template to fold, matrix cycles / 4 of the live fragments only). One measured
+// point: the vendored corpus, ratio 2.02 with all 48 fragments multiplied, gained 1.21x (DESIGN.md
+// section 4); with its 29 live ones the ratio is 2.74. The constant sits halfway between break-even
+// on paper and the first point; it is not calibrated on a second corpus.
 constexpr double kMfmaPayRatio = 1.5;
 constexpr int64_t kMfmaMaxFragBytes = 96 * 1024;   // one 12-wave workgroup per CU: 3 waves per SIMD
 
-// Shape and costs of the stage for a layout and its entries (no slot order needed).
-void plan_mfma(const dice_templates* t, const CompactLayout& L, const std::vector<Entry>& entries, MfmaTables& m) {
+// Shape of the stage for a layout (no word or slot order needed).
+void plan_mfma(const dice_templates* t, const CompactLayout& L, MfmaTables& m) {
     const int32_t qb = (L.bit_dwords + 3) / 4, np = (qb + 1) / 2;
     m.ksteps = 4 * np;
     m.ntiles = (t->n_templates + 31) / 32;
+    m.eligible = L.bit_dwords > 0 && (int64_t)m.ksteps * m.ntiles * 1024 <= kMfmaMaxFragBytes;
+    m.rows.assign((size_t)32 * m.ntiles, -1);
+    for (int32_t i = 0; i < t->n_templates; ++i) m.rows[(size_t)i] = i;
+}
+
+// Costs of the stage once its tables stand: only live fragments take matrix cycles.
+void cost_mfma(const dice_templates* t, const std::vector<Entry>& entries, MfmaTables& m) {
     m.valu_cost = 0;
     for (const Entry& e : entries)
         if (!e.sum) m.valu_cost += entry_cost(e);
-    m.stage_cost = 2 * 5 * (int64_t)m.ksteps + 3 * (int64_t)t->n_templates + (int64_t)m.ksteps * m.ntiles * 2 * 32 / 4;
-    m.eligible = L.bit_dwords > 0 && (int64_t)m.ksteps * m.ntiles * 1024 <= kMfmaMaxFragBytes;
+    const int64_t frags = m.eligible ? m.n_live : (int64_t)m.ksteps * m.ntiles;
+    m.stage_cost = 2 * 5 * (int64_t)m.ksteps + 3 * (int64_t)t->n_templates + frags * 2 * 32 / 4;
     m.pays = m.eligible && (double)m.valu_cost > kMfmaPayRatio * (double)m.stage_cost;
+}
+
+// The bit region's dwords in K-step order: K-step s multiplies dwords 8 (s / 4) + s % 4 (lane half 0)
+// and that + 4 (half 1), so a run of words laid along this sequence touches the fewest K-steps. The
+// last pair of quads may be short: its K-steps then carry 32 elements, or none. ks_of[i] is the
+// K-step of the i-th dword of the sequence (non-decreasing).
+std::vector<int32_t> kstep_dwords(int32_t bit_dwords, int32_t ksteps, std::vector<int32_t>& ks_of) {
+    std::vector<int32_t> seq;
+    ks_of.clear();
+    for (int32_t s = 0; s < ksteps; ++s)
+        for (int32_t h = 0; h < 2; ++h) {
+            const int32_t dw = 8 * (s / 4) + 4 * h + s % 4;
+            if (dw >= bit_dwords) continue;
+            seq.push_back(dw);
+            ks_of.push_back(s);
+        }
+    return seq;
+}
+
+// Live fragments of the grouped bit region [a words of block 0 only | both | b of block 1 only] laid
+// along kstep_dwords: block 0 is live on the K-steps of [0, a + both), block 1 on those of
+// [a, a + both + b). Padding rule: the bit region has `slack` = 32 bit_dwords - n_bits unused bits,
+// and 0 <= pad <= slack of them may follow the first group, which starts block 1 on a later K-step
+// at the price of ending both blocks later; the smallest pad with the fewest live fragments is taken.
+int32_t live_fragments(int32_t a, int32_t both, int32_t b, int32_t slack, const std::vector<int32_t>& ks_of, int32_t* pad) {
+    int32_t best = -1;
+    for (int32_t p = 0; p <= (a > 0 && both + b > 0 ? slack : 0); ++p) {
+        int32_t n = 0;
+        if (a + both > 0) n += ks_of[(size_t)((both > 0 ? a + p + both : a) - 1) / 32] + 1;
+        if (both + b > 0) n += ks_of[(size_t)(a + p + both + b - 1) / 32] - ks_of[(size_t)(a + p) / 32] + 1;
+        if (best < 0 || n < best) {
+            best = n;
+            if (pad) *pad = p;
+        }
+    }
+    return best;
+}
+
+// Row assignment for two blocks (32 < T <= 64): which templates share a 32-row block, so that with
+// the bit region grouped by block the fewest (K-step, block) fragments are live; on a tie the fewest
+// words that touch both blocks. Deterministic local search from two fixed starts ([0, 32) | [32, T),
+// and the T - 32 templates of the fewest bit words as block 1), the better end taken: sweeps
+// over all swaps of two templates across the blocks and all moves of one template to the other block
+// (<= 32 per block), each taken as soon as it improves, until a sweep changes nothing. `rows` holds
+// per template a bitset over the n bit words (W 64-bit words each). A block touches the words in the union
+// of its rows; with the union of each block without each of its templates at hand (`ex`, rebuilt
+// when a move is taken) a candidate costs 2 W ORs and popcounts. Returns block 0's template set.
+uint64_t assign_rows(int32_t T, const std::vector<uint64_t>& rows, int32_t W, int32_t n, int32_t slack,
+                     const std::vector<int32_t>& ks_of) {
+    const uint64_t all = T >= 64 ? ~0ull : (1ull << T) - 1;
+    const uint64_t* R = rows.data();
+    std::vector<uint64_t> ex((size_t)T * W), full((size_t)2 * W), pre((size_t)(T + 1) * W);
+    auto rebuild = [&](uint64_t m0) {
+        for (int blk = 0; blk < 2; ++blk) {
+            std::vector<int32_t> list;
+            for (int32_t i = 0; i < T; ++i)
+                if ((int)((m0 >> i) & 1) != blk) list.push_back(i);   // block 0 is the set bits of m0
+            const size_t k = list.size();
+            std::fill(pre.begin(), pre.begin() + W, 0ull);
+            for (size_t x = 0; x < k; ++x)
+                for (int32_t w = 0; w < W; ++w) pre[(x + 1) * W + w] = pre[x * W + w] | R[(size_t)list[x] * W + w];
+            for (int32_t w = 0; w < W; ++w) full[(size_t)blk * W + w] = pre[k * W + w];
+            std::vector<uint64_t> suf((size_t)W, 0ull);
+            for (size_t x = k; x-- > 0;) {
+                for (int32_t w = 0; w < W; ++w) {
+                    ex[(size_t)list[x] * W + w] = pre[x * W + w] | suf[(size_t)w];
+                    suf[(size_t)w] |= R[(size_t)list[x] * W + w];
+                }
+            }
+        }
+    };
+    // cost of block 0 touching x0 | y0 and block 1 touching x1 | y1 (y may be null)
+    auto cost = [&](const uint64_t* x0, const uint64_t* y0, const uint64_t* x1, const uint64_t* y1) {
+        int32_t p0 = 0, p1 = 0;
+        for (int32_t w = 0; w < W; ++w) {
+            p0 += __builtin_popcountll(x0[w] | (y0 ? y0[w] : 0ull));
+            p1 += __builtin_popcountll(x1[w] | (y1 ? y1[w] : 0ull));
+        }
+        const int32_t both = p0 + p1 - n;
+        return std::make_pair(live_fragments(n - p1, both, n - p0, slack, ks_of, nullptr), both);
+    };
+    auto search = [&](uint64_t m0) {
+        rebuild(m0);
+        auto cur = cost(&full[0], nullptr, &full[(size_t)W], nullptr);
+        for (int sweep = 0; sweep < 64; ++sweep) {
+            bool improved = false;
+            auto take = [&](const std::pair<int32_t, int32_t>& c, uint64_t cand) {
+                if (!(c < cur)) return;
+                cur = c;
+                m0 = cand;
+                improved = true;
+                rebuild(m0);
+            };
+            for (int32_t i = 0; i < T; ++i) {
+                for (int32_t j = i + 1; j < T; ++j) {
+                    if (!(((m0 >> i) ^ (m0 >> j)) & 1)) continue;
+                    const int32_t i0 = ((m0 >> i) & 1) ? i : j, i1 = i0 == i ? j : i;   // i0 leaves block 0, i1 block 1
+                    take(cost(&ex[(size_t)i0 * W], R + (size_t)i1 * W, &ex[(size_t)i1 * W], R + (size_t)i0 * W),
+                         m0 ^ (1ull << i) ^ (1ull << j));
+                }
+                const bool in0 = (m0 >> i) & 1;
+                const int n0 = __builtin_popcountll(m0);
+                if (in0 ? T - n0 >= 32 : n0 >= 32) continue;   // the other block is full
+                if (in0)
+                    take(cost(&ex[(size_t)i * W], nullptr, &full[(size_t)W], R + (size_t)i * W), m0 ^ (1ull << i));
+                else
+                    take(cost(&full[0], R + (size_t)i * W, &ex[(size_t)i * W], nullptr), m0 ^ (1ull << i));
+            }
+            if (!improved) break;
+        }
+        return std::make_pair(cur, m0);
+    };
+    // second start: the T - 32 templates of the fewest bit words in block 1 (index breaks ties)
+    std::vector<std::pair<int32_t, int32_t>> weight;
+    for (int32_t i = 0; i < T; ++i) {
+        int32_t c = 0;
+        for (int32_t w = 0; w < W; ++w) c += __builtin_popcountll(R[(size_t)i * W + w]);
+        weight.push_back({c, i});
+    }
+    std::sort(weight.begin(), weight.end());
+    uint64_t light = 0;
+    for (int32_t k = 0; k < T - 32; ++k) light |= 1ull << weight[(size_t)k].second;
+    const auto r0 = search(0xFFFFFFFFull), r1 = search(all & ~light);
+    return r1.first < r0.first ? r1.second : r0.second;
+}
+
+// Row map and word grouping of a two-block stage. The templates of block 0 (assign_rows) take device
+// rows 0.., the others rows 32.., ascending; the bit words are re-placed as the stable partition
+// [block 0 only | both | block 1 only] along kstep_dwords, their relative order inside a group as
+// place_words left it. Count fields, n_bits and bit_dwords do not change.
+void group_bits(const dice_templates* t, const std::vector<uint64_t>& col, CompactLayout& L, MfmaTables& m) {
+    const int32_t T = t->n_templates, V = t->n_vocab;
+    std::vector<int32_t> ks_of;
+    const std::vector<int32_t> seq = kstep_dwords(L.bit_dwords, m.ksteps, ks_of);
+    std::vector<int32_t> word((size_t)L.n_bits, -1);   // bit words in their present order
+    for (int32_t v = 0; v < V; ++v)
+        if (L.dest[(size_t)v] >= 0) word[(size_t)L.dest[(size_t)v]] = v;
+    const int32_t W = (L.n_bits + 63) / 64;
+    std::vector<uint64_t> rows((size_t)T * W, 0ull);   // per template: the bit words it holds
+    for (int32_t k = 0; k < L.n_bits; ++k)
+        for (uint64_t c = col[(size_t)word[(size_t)k]]; c; c &= c - 1)
+            rows[(size_t)__builtin_ctzll(c) * W + k / 64] |= 1ull << (k % 64);
+    const int32_t slack = 32 * L.bit_dwords - L.n_bits;
+    const uint64_t all = T >= 64 ? ~0ull : (1ull << T) - 1;
+    const uint64_t m0 = assign_rows(T, rows, W, L.n_bits, slack, ks_of), m1 = all & ~m0;
+    m.rows.assign(64, -1);
+    for (int32_t i = 0, r0 = 0, r1 = 32; i < T; ++i) m.rows[(size_t)(((m0 >> i) & 1) ? r0++ : r1++)] = i;
+    std::vector<int32_t> group[3];
+    for (int32_t v : word) {
+        const bool in0 = (col[(size_t)v] & m0) != 0, in1 = (col[(size_t)v] & m1) != 0;
+        group[in0 && in1 ? 1 : in0 ? 0 : 2].push_back(v);
+    }
+    int32_t pad = 0;
+    live_fragments((int32_t)group[0].size(), (int32_t)group[1].size(), (int32_t)group[2].size(), slack, ks_of, &pad);
+    int32_t lp = 0;
+    for (int g = 0; g < 3; ++g) {
+        for (int32_t v : group[g]) {
+            L.dest[(size_t)v] = 32 * seq[(size_t)lp / 32] + lp % 32;
+            ++lp;
+        }
+        if (g == 0) lp += pad;
+    }
 }
 
 // Tile slot of every layout quad.
@@ -276,6 +446,9 @@ void build_mfma_tables(const dice_templates* t, const CompactLayout& L, const st
         if (!e.sum) mask[(size_t)e.tpl * L.bit_dwords + e.dword] = e.mask;
     m.frag.assign((size_t)m.ksteps * m.ntiles * 64 * 4, 0u);
     m.map.assign((size_t)m.ksteps * 64, -1);
+    std::vector<char> used((size_t)32 * std::max(1, L.bit_dwords), 0);   // bit positions that hold a word
+    for (int32_t p : L.dest)
+        if (p >= 0) used[(size_t)p] = 1;
     for (int32_t s = 0; s < m.ksteps; ++s) {
         for (int32_t h = 0; h < 2; ++h) {
             const int32_t q = 2 * (s / 4) + h, dw = 4 * q + s % 4;
@@ -283,7 +456,7 @@ void build_mfma_tables(const dice_templates* t, const CompactLayout& L, const st
             const int32_t tile_dword = 4 * m.slots[(size_t)q] + s % 4;
             for (int32_t e = 0; e < 32; ++e) {   // element e = 8 k + i: nibble i of fragment dword k, bit 4 i + k
                 const int32_t bit = 4 * (e % 8) + e / 8;
-                if (32 * dw + bit < L.n_bits) m.map[(size_t)s * 64 + 32 * h + e] = 32 * tile_dword + bit;
+                if (used[(size_t)(32 * dw + bit)]) m.map[(size_t)s * 64 + 32 * h + e] = 32 * tile_dword + bit;
             }
             for (int32_t tp = 0; tp < T; ++tp) {
                 const uint32_t v = mask[(size_t)tp * L.bit_dwords + dw];
@@ -295,6 +468,23 @@ void build_mfma_tables(const dice_templates* t, const CompactLayout& L, const st
             }
         }
     }
+    // the device table: rows gathered through rows[]; a fragment is live iff it has a non-zero element
+    m.dfrag.assign(m.frag.size(), 0u);
+    m.live.assign((size_t)m.ksteps * m.ntiles, 0);
+    m.n_live = 0;
+    for (int32_t s = 0; s < m.ksteps; ++s)
+        for (int32_t j = 0; j < m.ntiles; ++j) {
+            uint32_t any = 0;
+            for (int32_t lane = 0; lane < 64; ++lane) {
+                const int32_t tp = m.rows[(size_t)(32 * j + lane % 32)];
+                if (tp < 0) continue;
+                const uint32_t* src = &m.frag[(((size_t)s * m.ntiles + tp / 32) * 64 + 32 * (lane / 32) + tp % 32) * 4];
+                uint32_t* dst = &m.dfrag[(((size_t)s * m.ntiles + j) * 64 + lane) * 4];
+                for (int k = 0; k < 4; ++k) any |= dst[k] = src[k];
+            }
+            m.live[(size_t)s * m.ntiles + j] = any != 0;
+            m.n_live += any != 0;
+        }
 }
 
 // Repack pieces for dice_pack_compact, per tile dword in slot order (`qperm` applied).
@@ -548,9 +738,11 @@ const char* kMatrixOffer = R"HIP(
 // host (dice_mfma_frag, staged in LDS once per workgroup); files are the B operand: lane (r, h)
 // loads whole quads of file 32 m + r -- lane half h takes every other bit quad, a quad's four
 // dwords serve four K-steps -- and widens a dword with 5 VALU (widen_a). Accumulator register g of
-// lane (c, h) is template 32 j + (g & 3) + 8 (g >> 2) + 4 h of file 32 m + c, so one
-// v_permlane32_swap of the m = 0 and m = 1 registers leaves lane l with two templates' overlaps
-// of file l: no LDS transpose. A workgroup of MWK = 12 waves walks a contiguous share of the tiles,
+// lane (c, h) is device row 32 j + (g & 3) + 8 (g >> 2) + 4 h of file 32 m + c, so one
+// v_permlane32_swap of the m = 0 and m = 1 registers leaves lane l with two rows' overlaps
+// of file l: no LDS transpose. Which template a row holds is the plan's choice (MfmaTables::rows):
+// with the bit region grouped by block, a (K-step, block) fragment that is all zero is neither read
+// from LDS nor multiplied, and a K-step that is live in no block is not widened. A workgroup of MWK = 12 waves walks a contiguous share of the tiles,
 // wave w taking every MWK-th; the next tile's quads are requested as this tile's K-steps retire
 // them. Match mode only: the matrix kernels, bound by their 600 B per file of stores, measured
 // 17% slower with the stage and keep the VALU program.
@@ -588,6 +780,9 @@ __device__ __forceinline__ v8i frag8(uint4 v) {
 #define MFMA_FOLD1(C0, C1, G, TA) { typedef u32 u32x2_ __attribute__((ext_vector_type(2))); \
     const u32x2_ r_ = __builtin_amdgcn_permlane32_swap((u32)C0[G], (u32)C1[G], false, false); \
     acc[TA] += r_[0]; }
+#define MFMA_FOLD1B(C0, C1, G, TB) { typedef u32 u32x2_ __attribute__((ext_vector_type(2))); \
+    const u32x2_ r_ = __builtin_amdgcn_permlane32_swap((u32)C0[G], (u32)C1[G], false, false); \
+    acc[TB] += r_[1]; }
 // Workgroup head: template fragments into LDS, the workgroup's share of the tiles, the wave's first
 // tile and its quads
 #define MFMA_HEAD \
@@ -783,14 +978,15 @@ std::string valu_prologue(const Program& p) {
 }
 
 // FILE_PROLOGUE_MFMA, the matrix-core form of the prologue (kMfmaPrelude): count quads requested
-// lane per file, the K-steps pair by pair of bit quads with the next tile's pair requested behind
-// them, the fold into acc[], then the count entries as in the VALU program. With it the MFMA_QDECL
+// lane per file, the live K-steps pair by pair of bit quads (one fragment read and two matrix
+// instructions per live block) with the next tile's pair requested behind them, the fold into acc[]
+// through the row map, then the count entries as in the VALU program. With it the MFMA_QDECL
 // and MFMA_QLOAD macros: per-lane quad offsets (lane half h takes the odd quad of each pair),
 // declarations, loads.
 void emit_mfma_prologue(std::ostringstream& s, const dice_templates* t, const Program& p) {
     const MfmaTables& m = p.mf;
     const std::vector<Entry>& dm = p.sched.dm;
-    const int32_t np = m.ksteps / 4, nj = m.ntiles, T = t->n_templates;
+    const int32_t np = m.ksteps / 4, nj = m.ntiles;
     const size_t ns = p.sched.range.size();
     std::ostringstream o;
     o << kAccDecl;
@@ -801,31 +997,49 @@ void emit_mfma_prologue(std::ostringstream& s, const dice_templates* t, const Pr
         crange[i] = {b, p.sched.range[i].second};
         if (b < p.sched.range[i].second) o << "const uint4 cq_" << i << " = ldq(fp + " << i * 64 << ");\n";
     }
-    for (int32_t j = 0; j < nj; ++j) o << "v16f c" << j << "_0 = {}, c" << j << "_1 = {};\n";
+    // DICE_PROG_DIAG=nomfma (results wrong): neither fragment reads nor matrix instructions; the
+    // widened file operands and the accumulators are kept alive through empty asm statements
+    const bool no_mfma = p.opts.diag == ProgramOptions::kNoMfma;
+    std::vector<char> blive((size_t)nj, 0);   // blocks with a live fragment: the others have no accumulators
+    for (int32_t ks = 0; ks < m.ksteps; ++ks)
+        for (int32_t j = 0; j < nj; ++j) blive[(size_t)j] |= m.live[(size_t)ks * nj + j];
+    for (int32_t j = 0; j < nj; ++j) {
+        if (!blive[(size_t)j]) continue;
+        o << "v16f c" << j << "_0 = {}, c" << j << "_1 = {};\n";
+        if (no_mfma) o << "asm volatile(\"\" : \"+v\"(c" << j << "_0), \"+v\"(c" << j << "_1));\n";
+    }
     const char* comp = "xyzw";
     for (int32_t u = 0; u < np; ++u) {
         for (int32_t d = 0; d < 4; ++d) {
             const int32_t ks = 4 * u + d;
             bool any = false;
-            for (int32_t e = 0; e < 64; ++e) any = any || m.map[(size_t)ks * 64 + e] >= 0;
-            if (!any) continue;
+            for (int32_t j = 0; j < nj; ++j) any = any || m.live[(size_t)ks * nj + j];
+            if (!any) continue;   // live in no block: not widened
             o << "{ const v8i b0_ = widen_a(q0_" << u << "." << comp[d] << "), b1_ = widen_a(q1_" << u << "."
               << comp[d] << ");\n";
-            for (int32_t j = 0; j < nj; ++j)
+            if (no_mfma)
+                o << "asm volatile(\"\" :: \"v\"(b0_[0]), \"v\"(b0_[1]), \"v\"(b0_[2]), \"v\"(b0_[3]), \"v\"(b1_[0]), "
+                     "\"v\"(b1_[1]), \"v\"(b1_[2]), \"v\"(b1_[3]));\n";
+            for (int32_t j = 0; j < nj && !no_mfma; ++j) {
+                if (!m.live[(size_t)ks * nj + j]) continue;
                 o << "{ const v8i a_ = frag8(tfrag[" << (ks * nj + j) * 64 << " + ll_]); c" << j << "_0 = MFMA44(a_, b0_, c"
                   << j << "_0); c" << j << "_1 = MFMA44(a_, b1_, c" << j << "_1); }\n";
+            }
             o << "}\n";
         }
         o << "q0_" << u << " = ldq(nq_ + o_" << u << "); q1_" << u << " = ldq(nq_ + o_" << u << " + 32);\n";
     }
+    // the fold names the templates through the row map: a pad can sit on either side of a pair
     for (int32_t j = 0; j < nj; ++j)
-        for (int32_t g = 0; g < 16; ++g) {
-            const int32_t ta = 32 * j + (g & 3) + 8 * (g >> 2), tb = ta + 4;
-            if (ta >= T) continue;
-            if (tb < T)
-                o << "MFMA_FOLD2(c" << j << "_0, c" << j << "_1, " << g << ", " << ta << ", " << tb << ")\n";
-            else
-                o << "MFMA_FOLD1(c" << j << "_0, c" << j << "_1, " << g << ", " << ta << ")\n";
+        for (int32_t g = 0; g < 16 && blive[(size_t)j]; ++g) {
+            const int32_t ra = 32 * j + (g & 3) + 8 * (g >> 2);
+            const int32_t ta = m.rows[(size_t)ra], tb = m.rows[(size_t)ra + 4];
+            if (ta < 0 && tb < 0) continue;
+            o << (ta >= 0 && tb >= 0 ? "MFMA_FOLD2" : ta >= 0 ? "MFMA_FOLD1" : "MFMA_FOLD1B") << "(c" << j << "_0, c" << j
+              << "_1, " << g;
+            if (ta >= 0) o << ", " << ta;
+            if (tb >= 0) o << ", " << tb;
+            o << ")\n";
         }
     for (size_t i = 0; i < ns; ++i) {
         if (crange[i].first == crange[i].second) continue;
@@ -968,17 +1182,26 @@ Program plan_program(const dice_templates* t, const ProgramOptions& opts) {
     Program p;
     p.opts = opts;
     const int32_t w64 = (t->n_vocab + 63) / 64;
+    std::vector<uint64_t> col;   // compact tile: template-membership column per word
     if (opts.compact) {
-        derive_layout(t, p.layout, p.prog);
+        col = word_columns(t);
+        derive_layout(t, col, p.layout, p.prog);
         p.wq = p.layout.quads;
     } else {
         p.prog = build_entries(t, w64);
         p.wq = (w64 + 1) / 2;
     }
+    if (opts.compact) {
+        plan_mfma(t, p.layout, p.mf);
+        if (p.mf.eligible && p.mf.ntiles == 2) {   // two blocks: rows assigned, the bit region grouped by block
+            group_bits(t, col, p.layout, p.mf);
+            build_compact_entries(t, col, p.layout, p.prog);
+        }
+    }
     p.sched = build_schedule(p.prog, p.wq);
     if (opts.compact) {
-        plan_mfma(t, p.layout, p.prog, p.mf);
         if (p.mf.eligible) build_mfma_tables(t, p.layout, p.prog, p.sched.qperm, p.mf);
+        cost_mfma(t, p.prog, p.mf);
         p.mfma_forced = opts.match == ProgramOptions::kMfma && p.mf.eligible;
         p.mfma = p.mfma_forced || (opts.match != ProgramOptions::kValu && p.mf.pays);
         p.pack_lists = build_pack_lists(p.layout, p.sched.qperm, t->n_vocab);
@@ -1004,9 +1227,11 @@ std::string emit_program(const dice_templates* t, const Program& p) {
     }
     if (p.mfma) {
         // the match kernel with the matrix-core accumulate stage, device compile only
+        s << "// matrix-core stage: ksteps=" << p.mf.ksteps << " blocks=" << p.mf.ntiles << " live=" << p.mf.n_live
+          << " valu_cost=" << p.mf.valu_cost << " stage_cost=" << p.mf.stage_cost << "\n";
         s << "#ifdef __HIP_DEVICE_COMPILE__\n#define MFMA_FRAGS " << p.mf.ksteps * p.mf.ntiles << "\n";
-        s << "__device__ const u32 dice_mfma_frag[" << p.mf.frag.size() << "] __attribute__((aligned(16))) = {\n" << std::hex;
-        for (size_t i = 0; i < p.mf.frag.size(); ++i) s << "0x" << p.mf.frag[i] << (i % 16 == 15 ? ",\n" : ",");
+        s << "__device__ const u32 dice_mfma_frag[" << p.mf.dfrag.size() << "] __attribute__((aligned(16))) = {\n" << std::hex;
+        for (size_t i = 0; i < p.mf.dfrag.size(); ++i) s << "0x" << p.mf.dfrag[i] << (i % 16 == 15 ? ",\n" : ",");
         s << std::dec << "};\n" << kMfmaPrelude;
         emit_mfma_prologue(s, t, p);
         s << "#define MWK " << kMfmaMatchWaves << "\n#undef ACC_INIT\n#define ACC_INIT(i) ((u32)(i) << 24)\n" << kMatchKernelMfma

@@ -22,7 +22,7 @@ constexpr int kMfmaMatchWaves = 12;     // MWK of the generated matrix-core matc
 // dice_create and in the exports; nothing below reads the environment).
 struct ProgramOptions {
     enum Match { kAuto, kValu, kMfma };
-    enum Diag { kNone, kNoAcc, kNoEpi, kTiming };
+    enum Diag { kNone, kNoAcc, kNoEpi, kTiming, kNoMfma };
     bool compact = true;    // DICE_PROG_LAYOUT: class-count tile, or (`bits`) the full-bitset tile
     Match match = kAuto;    // DICE_PROG_MATCH: `mfma` takes the matrix-core stage wherever it is eligible,
                             // `valu` never; by default the cost rule decides
@@ -73,13 +73,20 @@ struct PackPiece {
 
 // Tables of the matrix-core accumulate stage over the compact tile's bit region (kMfmaPrelude in
 // dice_program_gen.cpp). K-step s takes, per lane half h, one tile dword: dword s % 4 of
-// the quad in slot slots[2 (s / 4) + h] (-1: none, the template elements are zero).
+// the quad in slot slots[2 (s / 4) + h] (-1: none, the template elements are zero). The device
+// holds the templates in the rows assign_rows chose (rows[], two blocks of 32): with the bit region
+// grouped by block (group_bits) many (K-step, block) fragments are all zero, and the kernel neither
+// reads nor multiplies those (live[]).
 struct MfmaTables {
     int32_t ksteps = 0;               // K-steps of 64 elements (4 per pair of bit quads)
     int32_t ntiles = 0;               // 32-template tiles
     std::vector<int32_t> slots;       // [ksteps / 2] tile slot of the quad each lane half loads (-1: padding)
-    std::vector<uint32_t> frag;       // [ksteps][ntiles][64][4] pre-widened template fragments
+    std::vector<uint32_t> frag;       // [ksteps][ntiles][64][4] pre-widened template fragments, row 32 j + r = template 32 j + r
     std::vector<int32_t> map;         // [ksteps][64] tile bit carried by element e of half h (at 32 h + e), or -1
+    std::vector<int32_t> rows;        // [32 ntiles] template in device row 32 j + r, or -1 (padding)
+    std::vector<uint8_t> live;        // [ksteps][ntiles] 1: the fragment of device block j has a non-zero element
+    std::vector<uint32_t> dfrag;      // frag with its rows gathered through rows[]: the device table dice_mfma_frag
+    int32_t n_live = 0;               // fragments the kernel reads and multiplies
     int64_t valu_cost = 0;            // VALU instructions of the bit entries the stage replaces
     int64_t stage_cost = 0;           // the stage in VALU-issue units: fixed VALU + matrix cycles / 4
     bool eligible = false;            // a bit region, and the fragments fit in LDS at >= 2 waves per SIMD
