@@ -261,6 +261,23 @@ void dice_host_free(void *ptr);
 int dice_batch_download_rows(dice_batch *batch, uint64_t *bits, uint32_t *wordset_size, uint64_t *field_mask,
                              void *stream);
 
+/* ---- ContentHelper#content_hash on the device --------------------------------------------
+ * content_hash (content_helper.rb:136-138: DIGEST.hexdigest content_normalized, SHA-1; one of
+ * ProjectFile's HASH_METHODS, project_file.rb:17,97) of the texts dice_batch_upload_text left
+ * resident, one lane per file. A text with a non-ASCII character is resident with that character as
+ * the byte 0x80, so its bytes are not the UTF-8 of content_normalized: such a file is flagged and
+ * the caller hashes it.
+ *
+ * SHA-1 of every resident normalized text, asynchronous on `stream` (no host synchronization
+ * inside). DICE_E_STATE unless the batch's last upload was dice_batch_upload_text
+ * (dice_batch_set_rows and dice_batch_stream_probe leave the texts as they are). */
+int dice_batch_content_hash(dice_batch *batch, void *stream);
+/* D2H (synchronizes `stream`; content_helper.rb:136-138): digest [n][20] bytes, status [n]:
+ * 0 = digest is ContentHelper#content_hash of the file; 1 = the text holds a non-ASCII character
+ * (resident as 0x80), digest is of the resident bytes and the caller hashes that file's UTF-8 itself.
+ * NULL outputs are skipped; DICE_E_STATE if no hash was computed since the last upload. */
+int dice_batch_download_content_hash(dice_batch *batch, uint8_t *digest, uint8_t *status, void *stream);
+
 /* Build step (no device needed): generate + compile the corpus-specialized sparse program
  * with hiprtc for gfx950 and store it in the code-object cache; writes the cache path. */
 int dice_precompile(const dice_templates *templates, char *path, int32_t path_cap);

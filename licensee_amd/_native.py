@@ -31,7 +31,7 @@ EXPORTED_SYMBOLS = (
     'dice_batch_scored_pairs', 'dice_vocab_setup', 'dice_batch_upload_text', 'dice_batch_set_rows',
     'dice_batch_download_rows', 'dice_host_alloc', 'dice_host_free',
     'dice_program_source_compact', 'dice_program_layout', 'dice_program_mfma_tables', 'dice_ctx_program_stage',
-    'dice_program_mfma_rows',
+    'dice_program_mfma_rows', 'dice_batch_content_hash', 'dice_batch_download_content_hash',
 )
 DICE_GATHER_HOST = 0
 DICE_GATHER_DEVICE = 1
@@ -209,6 +209,8 @@ def load_library(path: str = LIB_PATH) -> ctypes.CDLL:
         'dice_batch_download_rows': (ctypes.c_int, [vp, vp, vp, vp, vp]),
         'dice_host_alloc': (ctypes.c_int, [i64, ctypes.POINTER(vp)]),
         'dice_host_free': (None, [vp]),
+        'dice_batch_content_hash': (ctypes.c_int, [vp, vp]),
+        'dice_batch_download_content_hash': (ctypes.c_int, [vp, vp, vp, vp]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)
@@ -542,6 +544,20 @@ class DeviceBatch:
         out = np.empty(self.n, np.int32)
         _check(load_library().dice_batch_download_exact(self._b, _ptr(out), stream or None))
         return out
+
+    def content_hash(self, stream: int = 0):
+        """SHA-1 of every resident normalized text (``dice_batch_content_hash``; asynchronous).
+        Needs the texts of :meth:`upload_text`: after another upload it raises (code -4)."""
+        _check(load_library().dice_batch_content_hash(self._b, stream or None))
+
+    def download_content_hash(self, stream: int = 0):
+        """The digests [n, 20] and status [n] of the last :meth:`content_hash` (status 1: the text
+        holds a non-ASCII character, resident as 0x80 -- the digest is of the resident bytes, not
+        ContentHelper#content_hash, which the caller computes from the file's UTF-8)."""
+        digest = np.empty((self.n, 20), np.uint8)
+        status = np.empty(self.n, np.uint8)
+        _check(load_library().dice_batch_download_content_hash(self._b, _ptr(digest), _ptr(status), stream or None))
+        return digest, status
 
     def deferred(self, stream: int = 0) -> int:
         """Files the bound-pruned kernel handed to the postings kernels in the last match."""

@@ -9,7 +9,9 @@ The reference evaluates ``[Copyright, Exact, Dice].map(new).find(&:match)`` per 
                                        masks (dice_batch_upload_text, content_helper.rb:108-110),
                                        Exact#match (dice_batch_exact: |W_F| == |W_t| and
                                        W_t ⊆ W_F, exact.rb:6-12) and Dice#match / #confidence
-                                       on the same resident batch
+                                       on the same resident batch; with ``content_hash=True``
+                                       also ContentHelper#content_hash (dice_batch_content_hash:
+                                       SHA-1 of the resident texts, content_helper.rb:136-138)
 (``wordset_on='host'`` scans and interns in the host threads instead, the round-5 split;
 ``exact_on='host'`` keeps Exact in the host threads too, the round-2 split.)
 
@@ -29,15 +31,22 @@ class Detection:
     license: License            # matched License, or License 'other'
     matcher: Optional[str]      # 'copyright' | 'exact' | 'dice' | None
     confidence: object          # 100 (copyright/exact), Float (dice), None (no matcher)
+    content_hash: Optional[str] = None   # content_hash (SHA-1 hex), BatchDetector(content_hash=True) only
 
 
 class BatchDetector:
     """One resident template corpus on the device + one native host context.
 
     ``engine`` defaults to the process-wide :func:`dice.default_engine` (the vendored
-    corpus); pass a :class:`dice.DiceEngine` to use another corpus or device."""
+    corpus); pass a :class:`dice.DiceEngine` to use another corpus or device.
 
-    def __init__(self, engine=None, nthreads: int = 8, exact_on: str = 'device', wordset_on: str = 'device'):
+    ``content_hash=True`` fills ``Detection.content_hash`` (ContentHelper#content_hash,
+    content_helper.rb:136-138) for every file, whatever matcher decided it: the device hashes the
+    normalized texts it already holds for the wordset scan, and the few files with a non-ASCII
+    character (resident as the byte 0x80) are hashed on the host threads."""
+
+    def __init__(self, engine=None, nthreads: int = 8, exact_on: str = 'device', wordset_on: str = 'device',
+                 content_hash: bool = False):
         from .dice import default_engine
         from .native_host import HostPrep
         if exact_on not in ('device', 'host'):
@@ -50,9 +59,15 @@ class BatchDetector:
         self.exact_on = exact_on if self.host.field_need is not None else 'host'
         # the device scan reports the non-vocabulary field words as mask bits for device Exact
         self.wordset_on = wordset_on if self.exact_on == 'device' else 'host'
+        if content_hash and self.wordset_on != 'device':
+            raise ValueError("content_hash=True hashes the normalized texts resident on the device, which only "
+                             "wordset_on='device' uploads (it resolved to 'host': wordset_on or exact_on is 'host', "
+                             "or the corpus has more than 64 field words outside the vocabulary)")
+        self.content_hash = bool(content_hash)
         self._batch = None          # one device batch, reused by every detect() and grown on demand
         self._pinned = [None, None]  # page-locked text buffers: batch k uploads from one while k + 1 fills the other
         self._turn = 0
+        self._pool = None           # threads of the content-hash completion (content_hash=True, on demand)
         if self.exact_on == 'device':
             self.engine.scorer.exact_setup(*exact_tables(self.engine.corpus, self.host))
         if self.wordset_on == 'device':
@@ -67,6 +82,9 @@ class BatchDetector:
         return self._batch
 
     def close(self):
+        if self._pool is not None:
+            self._pool.shutdown()
+            self._pool = None
         if self._batch is not None:
             self._batch.close()
             self._batch = None
@@ -129,6 +147,8 @@ class BatchDetector:
         n = len(off)
         b = self._device_batch(max(n, 1))
         st = b.upload_text(text, off, tl, ln, cc)
+        if self.content_hash:
+            b.content_hash()
         over = np.nonzero(st)[0]
         if over.size:
             sub = [contents[i] for i in over]
@@ -139,13 +159,51 @@ class BatchDetector:
         b.match(float(thr), confidence=True)
         exact = b.download_exact()
         best, _, score = b.download_match()
-        return copyright, exact, best, score
+        hashes = self._hashes(b, contents, filenames) if self.content_hash else None
+        return copyright, exact, best, score, hashes
+
+    def _hashes(self, b, contents, filenames) -> List[str]:
+        """content_hash per file as hex: the device digests, and for the files the device flagged
+        (a non-ASCII character, resident as 0x80) the SHA-1 of content_normalized's UTF-8 from the
+        host threads (the native normalize releases the GIL)."""
+        import hashlib
+        import numpy as np
+        digest, status = b.download_content_hash()
+        hx = digest.tobytes().hex()     # in bulk (as _detections: no per-file numpy work)
+        hashes = [hx[i:i + 40] for i in range(0, len(hx), 40)]
+        flagged = np.nonzero(status)[0].tolist()
+        if flagged:
+            # contiguous slices, one per thread: few hand-overs of the GIL between the native calls
+            k = max(1, min(self.nthreads, len(flagged) // 8))
+            parts = [flagged[len(flagged) * j // k:len(flagged) * (j + 1) // k] for j in range(k)]
+
+            def some(part):
+                sub = [contents[i] for i in part]
+                sfn = [filenames[i] for i in part] if filenames is not None else None
+                done = self.host.content_hashes(sub, sfn)
+                for j, i in enumerate(part):
+                    if done[j] is None:     # outside the native normalizer's envelope
+                        from .project_files import LicenseFile
+                        lf = LicenseFile(sub[j], sfn[j] if sfn is not None else 'LICENSE')
+                        done[j] = hashlib.sha1((lf.content_normalized() or '').encode('utf-8')).hexdigest()
+                return done
+            if k > 1:
+                if self._pool is None:
+                    from concurrent.futures import ThreadPoolExecutor
+                    self._pool = ThreadPoolExecutor(self.nthreads)
+                results = list(self._pool.map(some, parts))
+            else:
+                results = [some(parts[0])]
+            for part, done in zip(parts, results):
+                for i, h in zip(part, done):
+                    hashes[i] = h
+        return hashes
 
     def _score(self, prepped, thr) -> List[Detection]:
         """Device stage: Exact (device) + Dice#match/#confidence, then the matcher chain's order."""
         if prepped[0] == 'text':
-            copyright, exact, best, score = self._score_text(prepped, thr)
-            return self._detections(copyright, exact, best, score)
+            copyright, exact, best, score, hashes = self._score_text(prepped, thr)
+            return self._detections(copyright, exact, best, score, hashes)
         fb, copyright, third = prepped
         if self.exact_on == 'device':
             b = self._device_batch(max(fb.n, 1))
@@ -159,7 +217,7 @@ class BatchDetector:
             best, _, score = self.engine.scorer.match(fb, float(thr), confidence=True)
         return self._detections(copyright, exact, best, score)
 
-    def _detections(self, copyright, exact, best, score) -> List[Detection]:
+    def _detections(self, copyright, exact, best, score, hashes=None) -> List[Detection]:
         templates = self.engine.templates
         no_license, other = License.find('no-license'), License.find('other')
         # the matcher chain's order per file (Copyright, Exact, Dice, else 'other'), over Python lists
@@ -170,6 +228,13 @@ class BatchDetector:
         paused = gc.isenabled()
         gc.disable()
         try:
+            if hashes is not None:
+                return [Detection(no_license, 'copyright', 100, h) if c else
+                        Detection(templates[e], 'exact', 100, h) if e >= 0 else
+                        Detection(templates[bi], 'dice', sc, h) if bi >= 0 else
+                        Detection(other, None, None, h)
+                        for c, e, bi, sc, h in zip(copyright.tolist(), exact.tolist(), best.tolist(), score.tolist(),
+                                                   hashes)]
             return [Detection(no_license, 'copyright', 100) if c else
                     Detection(templates[e], 'exact', 100) if e >= 0 else
                     Detection(templates[bi], 'dice', sc) if bi >= 0 else

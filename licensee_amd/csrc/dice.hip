@@ -540,7 +540,7 @@ void dice_batch_destroy(dice_batch* b) {
     void* ptrs[] = {b->d_rows, b->d_tiles, b->d_wf,  b->d_len,    b->d_cc,    b->d_best,  b->d_ov,   b->d_score,
                     b->d_mov,  b->d_mscore, b->d_tki, b->d_tks, b->d_stage, b->d_pdense, b->d_ids, b->d_offs,
                     b->d_defer, b->d_ndefer, b->d_nscored, b->d_exact, b->d_fmask, b->d_text, b->d_toff,
-                    b->d_tlen, b->d_wstat, b->d_wcnt};
+                    b->d_tlen, b->d_wstat, b->d_wcnt, b->d_hdig, b->d_hstat, b->d_hcnt};
     for (void* p : ptrs)
         if (p) (void)hipFree(p);
     delete b;
@@ -587,6 +587,7 @@ int dice_batch_upload(dice_batch* b, const dice_files* f, void* stream) {
     b->n = n;
     b->n_long = 0;
     b->fmask_device = false;
+    b->text_state = 0;
     if (n == 0) return DICE_OK;
     HIP_TRY(hipMemcpyAsync(b->d_rows, f->bits, (size_t)n * c->w64 * 8, hipMemcpyHostToDevice, s));
     return dice::upload_tail(b, n, f->wordset_size, f->length, f->cc_false_positive, s);
@@ -602,6 +603,7 @@ int dice::upload_rows_resident(dice_batch* b, const dice_files* f, hipStream_t s
     b->n = f->n_files;
     b->n_long = 0;
     b->fmask_device = false;
+    b->text_state = 0;
     if (b->n == 0) return DICE_OK;
     return upload_tail(b, b->n, f->wordset_size, f->length, f->cc_false_positive, s);
 }
@@ -627,6 +629,7 @@ int dice_batch_upload_ids(dice_batch* b, int64_t n, const int64_t* offsets, cons
     b->n = n;
     b->n_long = 0;
     b->fmask_device = false;
+    b->text_state = 0;
     if (n == 0) return DICE_OK;
     const size_t need = (size_t)std::max<int64_t>(offsets[n], 1) * (size_t)id_bytes;
     if (need > b->ids_bytes) {

@@ -204,6 +204,12 @@ struct dice_batch {
     int32_t* d_tlen = nullptr;
     uint8_t* d_wstat = nullptr;
     uint32_t* d_wcnt = nullptr;
+    // dice_batch_content_hash (dice_hash.hip): 0 = the last upload left no text resident, 1 = the
+    // texts of dice_batch_upload_text are resident, 2 = and their digests are computed (or queued)
+    int32_t text_state = 0;
+    uint8_t* d_hdig = nullptr;      // [capacity][20] SHA-1 digests
+    uint8_t* d_hstat = nullptr;     // [capacity] 1 = the text holds a byte >= 0x80
+    uint32_t* d_hcnt = nullptr;     // the kernel's next-file counter
     // small-call batch: d_wf/d_len/d_cc/d_rows carved from d_in, results from d_out
     void *d_in = nullptr, *d_out = nullptr;
 };

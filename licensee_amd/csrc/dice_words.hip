@@ -822,6 +822,7 @@ int dice_batch_upload_text(dice_batch* b, int64_t n, const uint8_t* text, int64_
     if (!b->d_fmask && (rc = dice::grow(&b->d_fmask, dummy, cap8))) return rc;
     b->n = n;
     b->n_long = 0;
+    b->text_state = n == 0;   // (dice_batch_content_hash: the texts are resident once this call succeeds)
     if (n_overflow) *n_overflow = 0;
     if (n == 0) return DICE_OK;
     if (hipMemcpyAsync(b->d_text, text, (size_t)text_bytes, hipMemcpyHostToDevice, s) != hipSuccess ||
@@ -853,7 +854,9 @@ int dice_batch_upload_text(dice_batch* b, int64_t n, const uint8_t* text, int64_
         return fail(DICE_E_DEVICE, "wordset status download failed");
     if (n_overflow) *n_overflow = cnt[0];
     b->n_long = cnt[1];
-    return dice::upload_tail(b, n, nullptr, length, cc, s);
+    rc = dice::upload_tail(b, n, nullptr, length, cc, s);
+    b->text_state = rc == DICE_OK;
+    return rc;
 }
 
 int dice_batch_set_rows(dice_batch* b, int64_t k, const int64_t* index, const uint64_t* bits, const uint32_t* wordset_size,

@@ -191,6 +191,31 @@ class HostPrep:
         _load().lh_normalize(self._c, data, len(data), fn, 1 if is_file else 0, buf, n + 1)
         return buf.raw[:n].decode('utf-8')
 
+    def content_hashes(self, contents: Sequence[Union[str, bytes]], filenames: Optional[Sequence[str]] = None) -> list:
+        """ContentHelper#content_hash (content_helper.rb:136-138) of each file: the SHA-1 hex of the
+        native content_normalized's UTF-8, or None for a file outside the native envelope. One
+        normalization per file into a buffer reused over the call (a second only when the text
+        outgrows it), hashed where it lies; both release the GIL, so callers run this in threads."""
+        import hashlib
+        lib = _load()
+        out = []
+        cap, ba, cbuf = 0, None, None
+        for i, content in enumerate(contents):
+            data = content if isinstance(content, bytes) else content.encode('utf-8')
+            fn = filenames[i].encode('utf-8') if filenames is not None and filenames[i] else None
+            if cap < len(data) + 256:
+                cap = 2 * len(data) + 4096
+                ba = bytearray(cap)
+                cbuf = (ctypes.c_char * cap).from_buffer(ba)
+            n = lib.lh_normalize(self._c, data, len(data), fn, 1, cbuf, cap)
+            if n >= cap:    # (the text was not written)
+                cap = 2 * n + 4096
+                ba = bytearray(cap)
+                cbuf = (ctypes.c_char * cap).from_buffer(ba)
+                n = lib.lh_normalize(self._c, data, len(data), fn, 1, cbuf, cap)
+            out.append(None if n < 0 else hashlib.sha1(memoryview(ba)[:n]).hexdigest())
+        return out
+
     def prep_files(self, contents: Sequence[Union[str, bytes]], filenames: Optional[Sequence[str]] = None,
                    nthreads: int = 8, field_masks: bool = False) -> Tuple[FileBatch, np.ndarray, np.ndarray, np.ndarray]:
         """Returns (FileBatch, copyright flags, exact template index or -1, fell_back mask).
