@@ -613,14 +613,19 @@ __device__ __forceinline__ u32 bytesum(u32 x) { u32 r; asm("v_sad_u8 %0, %1, 0, 
 )HIP";
 
 // MATCH_FILE is the per-file body of both match kernels, from the scalar loads to the three result
-// stores; PROLOGUE names the accumulate stage (FILE_PROLOGUE or FILE_PROLOGUE_MFMA).
+// stores; PROLOGUE names the accumulate stage (FILE_PROLOGUE or FILE_PROLOGUE_MFMA). CC_ABOVE and
+// CC_BELOW form the cc flag: above the stage in the VALU kernel (MATCH_CC), while the matrix-core
+// kernel only requests the byte there, pins the scalar loads, and forms the flag below its stage
+// (MFMA_SCALARS_REQUESTED, MFMA_SCALARS_USED).
 const char* kMatchKernel = R"HIP(
 // running best: bo = template index << 24 | overlap (0xFF: none yet), bd = its denominator
-#define MATCH_FILE(PROLOGUE) \
-    const u32 wf = wfp[file]; \
-    const i32 lf = lenp[file]; \
-    const bool cc = ccp[file] != 0; \
+#define MATCH_CC const bool cc = ccp[file] != 0;
+#define MATCH_FILE(PROLOGUE, CC_ABOVE, CC_BELOW) \
+    u32 wf = wfp[file]; \
+    i32 lf = lenp[file]; \
+    CC_ABOVE \
     PROLOGUE \
+    CC_BELOW \
     const bool fast = CORPUS_FAST && wf < (1u << 20) && lf >= 0 && lf < (1 << 21); \
     u32 bo = 0xFF000000u; i32 bd = 1; \
     if (__all(fast)) { \
@@ -648,7 +653,7 @@ extern "C" __global__ __launch_bounds__(64 * WPB) void dice_prog_match(
 #if WAVE_TIMING
     const u64 t0_ = __builtin_amdgcn_s_memrealtime();
 #endif
-    MATCH_FILE(FILE_PROLOGUE)
+    MATCH_FILE(FILE_PROLOGUE, MATCH_CC, )
 #if WAVE_TIMING
     // diagnostics (DICE_PROG_DIAG=timing, results wrong): per wave its start and end real-time (100 MHz)
     // clock and the raw HW_ID / XCC_ID registers, in the tile's first output slots
@@ -783,26 +788,38 @@ __device__ __forceinline__ v8i frag8(uint4 v) {
 #define MFMA_FOLD1B(C0, C1, G, TB) { typedef u32 u32x2_ __attribute__((ext_vector_type(2))); \
     const u32x2_ r_ = __builtin_amdgcn_permlane32_swap((u32)C0[G], (u32)C1[G], false, false); \
     acc[TB] += r_[1]; }
-// Workgroup head: template fragments into LDS, the workgroup's share of the tiles, the wave's first
-// tile and its quads
+// The compiler sinks a load to its first use when nothing holds it: the scheduling barriers keep
+// the tile's loads where the text has them, and the scalars pass through an empty asm below the
+// stage, so that their first use (cc != 0 is a compare the compiler would otherwise do at once,
+// behind a wait that drains the whole load queue) stays below it.
+#define MFMA_PIN __builtin_amdgcn_sched_barrier(0);
+#define MFMA_SCALARS_REQUESTED u32 ccr_ = ccp[file]; MFMA_PIN
+#define MFMA_SCALARS_USED asm volatile("" : "+v"(wf), "+v"(lf), "+v"(ccr_)); const bool cc = ccr_ != 0;
+// Workgroup head: the workgroup's share of the tiles and the wave's first tile, whose quads are
+// requested before the template fragments go into LDS and fly during the fill (a wave without a
+// tile asks for tile 0, which every launch has, helps with the fill and leaves)
 #define MFMA_HEAD \
     __shared__ uint4 tfrag[MFMA_FRAGS * 64]; \
-    for (int i = threadIdx.x; i < MFMA_FRAGS * 64; i += 64 * MWK) tfrag[i] = ((const uint4*)dice_mfma_frag)[i]; \
-    __syncthreads(); \
     const int lane = threadIdx.x & 63; \
-    int ms_ = 0x7F7F7F7F; asm volatile("" : "+v"(ms_)); \
     const i64 nt_ = (n + 63) >> 6; \
     const i64 t1 = nt_ * (i64)(blockIdx.x + 1) / (i64)gridDim.x; \
     i64 tile = nt_ * (i64)blockIdx.x / (i64)gridDim.x + __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)); \
-    if (tile >= t1) return; \
     MFMA_QDECL \
-    { const uint4* nq_ = files + tile * (i64)(WQ * 64) + (lane & 31); MFMA_QLOAD }
-// Per tile: the quads of the wave's next tile (this one again after the last: loaded, never used)
+    { const uint4* nq_ = files + (tile < t1 ? tile : 0) * (i64)(WQ * 64) + (lane & 31); MFMA_PIN MFMA_QLOAD MFMA_PIN } \
+    for (int i = threadIdx.x; i < MFMA_FRAGS * 64; i += 64 * MWK) tfrag[i] = ((const uint4*)dice_mfma_frag)[i]; \
+    __syncthreads(); \
+    if (tile >= t1) return; \
+    int ms_ = 0x7F7F7F7F; asm volatile("" : "+v"(ms_));
+// Per tile: the quads of the wave's next tile. After its last tile a wave has none: the lane
+// offsets collapse (MFMA_NEXT) and the requests, which keep their place so that the loop has one
+// shape and one count of loads in flight, all fall on the 1 KiB of this tile's first quad.
 #define MFMA_TILE \
     const i64 file = tile * 64 + lane; \
     const uint4* fp = files + tile * (i64)(WQ * 64) + lane; \
-    const uint4* nq_ = files + (tile + MWK < t1 ? tile + MWK : tile) * (i64)(WQ * 64) + (lane & 31); \
+    const bool more_ = tile + MWK < t1; \
+    const uint4* nq_ = files + (more_ ? tile + MWK : tile) * (i64)(WQ * 64) + (lane & 31); \
     int ll_ = lane; asm volatile("" : "+v"(ll_));   /* fragment reads stay in the loop (and out of scratch) */
+#define MFMA_NEXT(o) (nq_ + (more_ ? (o) : 0))
 )HIP";
 
 const char* kMatchKernelMfma = R"HIP(
@@ -813,7 +830,7 @@ extern "C" __global__ __launch_bounds__(64 * MWK) void dice_prog_match_mfma(
     MFMA_HEAD
     for (; tile < t1; tile += MWK) {
         MFMA_TILE
-        MATCH_FILE(FILE_PROLOGUE_MFMA)
+        MATCH_FILE(FILE_PROLOGUE_MFMA, MFMA_SCALARS_REQUESTED, MFMA_SCALARS_USED)
     }
 }
 )HIP";
@@ -997,6 +1014,7 @@ void emit_mfma_prologue(std::ostringstream& s, const dice_templates* t, const Pr
         crange[i] = {b, p.sched.range[i].second};
         if (b < p.sched.range[i].second) o << "const uint4 cq_" << i << " = ldq(fp + " << i * 64 << ");\n";
     }
+    o << "MFMA_PIN\n";   // the count quads are requested here, above the K-steps
     // DICE_PROG_DIAG=nomfma (results wrong): neither fragment reads nor matrix instructions; the
     // widened file operands and the accumulators are kept alive through empty asm statements
     const bool no_mfma = p.opts.diag == ProgramOptions::kNoMfma;
@@ -1027,7 +1045,9 @@ void emit_mfma_prologue(std::ostringstream& s, const dice_templates* t, const Pr
             }
             o << "}\n";
         }
-        o << "q0_" << u << " = ldq(nq_ + o_" << u << "); q1_" << u << " = ldq(nq_ + o_" << u << " + 32);\n";
+        // the pair's registers are free: the next tile's pair, held in place
+        o << "MFMA_PIN\nq0_" << u << " = ldq(MFMA_NEXT(o_" << u << ")); q1_" << u << " = ldq(MFMA_NEXT(o_" << u
+          << ") + 32);\nMFMA_PIN\n";
     }
     // the fold names the templates through the row map: a pad can sit on either side of a pair
     for (int32_t j = 0; j < nj; ++j)
