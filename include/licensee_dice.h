@@ -17,7 +17,10 @@
  *   dice_similarity_matrix          Dice#matches_by_similarity / #licenses_by_similarity (full N x T
  *                                   scores + sorted top-k, no threshold cut)  dice.rb:34-41;
  *                                   also `licensee detect` "closest licenses" lib/licensee/commands/detect.rb:96-106
- *   dice_*_sharded                  the same two calls with the files sharded over several
+ *   dice_topk                       the first k entries of Dice#matches_by_similarity  dice.rb:34-41, which is
+ *                                   all `licensee detect` reads for "closest licenses"  detect.rb:96-106
+ *                                   (no N x T matrix is computed, stored or allocated)
+ *   dice_*_sharded                  the same calls with the files sharded over several
  *                                   devices of one node (the dice.rb:34-41 loop is per file)
  *   dice_batch_*                    device-resident batch variants of the two calls above
  *                                   (inputs as bitsets or as word-id lists)
@@ -125,6 +128,12 @@ int dice_similarity_matrix(dice_ctx *ctx, const dice_files *files,
                            uint32_t *overlap, double *score,
                            int32_t k, int32_t *topk_index, double *topk_score);
 
+/* The per-file top-k of dice_similarity_matrix alone (Dice#matches_by_similarity, dice.rb:34-41,
+ * cut to its first k entries as `licensee detect` cuts it, detect.rb:96-106): topk_index/topk_score
+ * [n][k] exactly as dice_similarity_matrix(k) fills them; k in [1, DICE_TOPK_MAX]. No N x T buffer
+ * is allocated or written on the device. */
+int dice_topk(dice_ctx *ctx, const dice_files *files, int32_t k, int32_t *topk_index, double *topk_score);
+
 /* ---- one node, several devices: the files of one call sharded over contexts ----------
  * The loop of Dice#matches_by_similarity (dice.rb:34-41) is independent per file, so a call
  * splits its files into n_ctx contiguous shards (shard i = files [n*i/n_ctx, n*(i+1)/n_ctx)),
@@ -153,6 +162,9 @@ int dice_match_sharded_confidence(dice_ctx *const *ctxs, int32_t n_ctx, const di
 int dice_similarity_matrix_sharded(dice_ctx *const *ctxs, int32_t n_ctx, const dice_files *files,
                                    int32_t gather_mode, uint32_t *overlap, double *score, int32_t k,
                                    int32_t *topk_index, double *topk_score);
+/* dice_topk sharded (dice.rb:34-41 per file, detect.rb:96-106); bit-identical to the one-context call. */
+int dice_topk_sharded(dice_ctx *const *ctxs, int32_t n_ctx, const dice_files *files, int32_t gather_mode,
+                      int32_t k, int32_t *topk_index, double *topk_score);
 /* The last sharded call on this thread: 1 = device gather, every shard on another device wrote
  * into ctxs[0]'s device through peer access; 0 = device gather with at least one such shard
  * through the runtime's staged copy; -1 = no peer path exercised: a host gather, a device gather
@@ -193,14 +205,32 @@ int dice_batch_scored_pairs(dice_batch *batch, int64_t *pairs, void *stream);
 /* Device-resident matrix results are template-major ([T][n] overlap/score, [k][n] top-k) so
  * every store is coalesced; dice_batch_download_matrix returns them row-major. */
 int dice_batch_matrix(dice_batch *batch, int32_t k, void *stream);
+/* The ranking of dice_batch_matrix(k) without the matrix (dice.rb:34-41 read for its first k entries,
+ * detect.rb:96-106): fills the batch's top-k index and score buffers exactly as dice_batch_matrix(k)
+ * does -- among potential_matches (CC filter applied), best first, the later template first on an
+ * exact tie, -1 / -1.0 padding (also for k > T) -- and nothing else: only the [n][k] buffers are
+ * allocated, the N x T buffers are neither allocated nor written, and the results of an earlier
+ * dice_batch_match stay as they are. k in [1, DICE_TOPK_MAX] (DICE_E_ARG otherwise). Asynchronous on
+ * `stream` with dice_batch_matrix's capture contract. */
+int dice_batch_topk(dice_batch *batch, int32_t k, void *stream);
+/* Bytes currently allocated for the batch's N x T overlap and score buffers: 0 until
+ * dice_batch_matrix has run on the batch (dice_batch_topk never allocates them), -1 for NULL. */
+int64_t dice_batch_matrix_bytes(const dice_batch *batch);
 /* D2H of results (synchronizes `stream`); NULL outputs are skipped.
  * dice_batch_download_matrix: overlap/score are [n][T]; topk_index/topk_score are [n][k] and
- * `k` must equal the k of the last dice_batch_matrix call on this batch (DICE_E_ARG
- * otherwise, so a caller's buffer is never written past its [n][k] extent). */
+ * `k` must equal the k of the last dice_batch_matrix / dice_batch_topk call on this batch (DICE_E_ARG
+ * otherwise, so a caller's buffer is never written past its [n][k] extent). When that call was
+ * dice_batch_topk the matrix on the device is absent or stale: a non-NULL overlap or score is
+ * DICE_E_STATE, the top-k outputs work as ever.
+ * dice_batch_download_topk (dice.rb:34-41, detect.rb:96-106): the [n][k] ranking, row-major whatever
+ * the device layout is, after dice_batch_topk(k) or dice_batch_matrix(k) with k > 0; DICE_E_STATE
+ * when the batch has had no ranking call, DICE_E_ARG for another k. */
 int dice_batch_download_match(dice_batch *batch, int32_t *best, uint32_t *overlap,
                               double *score, void *stream);
 int dice_batch_download_matrix(dice_batch *batch, uint32_t *overlap, double *score, int32_t k,
                                int32_t *topk_index, double *topk_score, void *stream);
+int dice_batch_download_topk(dice_batch *batch, int32_t k, int32_t *topk_index, double *topk_score,
+                             void *stream);
 /* Device pointers of the match results (int32 best, uint32 overlap, double score). */
 int dice_batch_result_ptrs(dice_batch *batch, void **best, void **overlap, void **score);
 /* Diagnostic: stream-read the resident tiles with trivial compute (read-ceiling probe). */

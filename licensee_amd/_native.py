@@ -32,6 +32,7 @@ EXPORTED_SYMBOLS = (
     'dice_batch_download_rows', 'dice_host_alloc', 'dice_host_free',
     'dice_program_source_compact', 'dice_program_layout', 'dice_program_mfma_tables', 'dice_ctx_program_stage',
     'dice_program_mfma_rows', 'dice_batch_content_hash', 'dice_batch_download_content_hash',
+    'dice_topk', 'dice_topk_sharded', 'dice_batch_topk', 'dice_batch_download_topk', 'dice_batch_matrix_bytes',
 )
 DICE_GATHER_HOST = 0
 DICE_GATHER_DEVICE = 1
@@ -211,6 +212,11 @@ def load_library(path: str = LIB_PATH) -> ctypes.CDLL:
         'dice_host_free': (None, [vp]),
         'dice_batch_content_hash': (ctypes.c_int, [vp, vp]),
         'dice_batch_download_content_hash': (ctypes.c_int, [vp, vp, vp, vp]),
+        'dice_topk': (ctypes.c_int, [vp, ctypes.POINTER(_Files), i32, vp, vp]),
+        'dice_topk_sharded': (ctypes.c_int, [vp, i32, ctypes.POINTER(_Files), i32, i32, vp, vp]),
+        'dice_batch_topk': (ctypes.c_int, [vp, i32, vp]),
+        'dice_batch_download_topk': (ctypes.c_int, [vp, i32, vp, vp, vp]),
+        'dice_batch_matrix_bytes': (i64, [vp]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)
@@ -223,7 +229,9 @@ def load_library(path: str = LIB_PATH) -> ctypes.CDLL:
 def _check(rc: int):
     if rc != DICE_OK:
         msg = load_library().dice_last_error().decode('utf-8', 'replace')
-        raise DiceError(f'dice error {rc}: {msg}')
+        err = DiceError(f'dice error {rc}: {msg}')
+        err.code = rc
+        raise err
 
 
 def _ptr(a: Optional[np.ndarray]):
@@ -351,6 +359,20 @@ class Scorer:
             _check(load_library().dice_similarity_matrix(self._ctx, ctypes.byref(st), _ptr(ov), _ptr(score), k,
                                                          _ptr(tki) if k else None, _ptr(tks) if k else None))
         return ov, score, tki, tks
+
+    def topk(self, files: FileBatch, k: int):
+        """``dice_topk``: the [n][k] top-k (index int32, score float64) of :meth:`matrix` alone --
+        Dice#matches_by_similarity cut to its first k entries, what ``licensee detect`` prints as
+        closest licenses. No [n][T] matrix is computed, stored or allocated."""
+        n, k = files.n, int(k)
+        if not 1 <= k <= DICE_TOPK_MAX:
+            raise ValueError(f'k must be in [1, {DICE_TOPK_MAX}]')
+        tki = np.empty((n, k), np.int32)
+        tks = np.empty((n, k), np.float64)
+        if n:
+            st = files._struct()
+            _check(load_library().dice_topk(self._ctx, ctypes.byref(st), k, _ptr(tki), _ptr(tks)))
+        return tki, tks
 
     def batch(self, capacity: int) -> 'DeviceBatch':
         return DeviceBatch(self, capacity)
@@ -510,6 +532,25 @@ class DeviceBatch:
         _check(load_library().dice_batch_matrix(self._b, int(k), stream or None))
         self.k = int(k)
 
+    def topk(self, k: int, stream: int = 0):
+        """``dice_batch_topk``: the ranking of :meth:`matrix` into the [n][k] buffers alone
+        (asynchronous); the N x T buffers are neither allocated nor written."""
+        _check(load_library().dice_batch_topk(self._b, int(k), stream or None))
+        self.k = int(k)
+
+    def download_topk(self, k: Optional[int] = None, stream: int = 0):
+        """The [n][k] ranking (index, score) of the last :meth:`topk` or :meth:`matrix` call; a
+        different ``k`` raises (DICE_E_ARG), as does a batch never ranked (DICE_E_STATE)."""
+        k = getattr(self, 'k', 0) if k is None else int(k)
+        tki = np.empty((self.n, max(k, 0)), np.int32)
+        tks = np.empty((self.n, max(k, 0)), np.float64)
+        _check(load_library().dice_batch_download_topk(self._b, k, _ptr(tki), _ptr(tks), stream or None))
+        return tki, tks
+
+    def matrix_bytes(self) -> int:
+        """Bytes allocated for the N x T overlap and score buffers (0 until :meth:`matrix` ran)."""
+        return int(load_library().dice_batch_matrix_bytes(self._b))
+
     def download_match(self, stream: int = 0):
         n = self.n
         best = np.empty(n, np.int32)
@@ -639,3 +680,17 @@ def matrix_sharded(scorers, files: FileBatch, k: int = 0, gather: int = DICE_GAT
                                                              _ptr(score), int(k), _ptr(tki) if k else None,
                                                              _ptr(tks) if k else None))
     return ov, score, tki, tks
+
+
+def topk_sharded(scorers, files: FileBatch, k: int, gather: int = DICE_GATHER_HOST):
+    """``dice_topk_sharded``: the [n][k] top-k of :meth:`Scorer.topk`, the files sharded."""
+    arr, n_ctx, _ = _ctx_array(scorers)
+    n, k = files.n, int(k)
+    if not 1 <= k <= DICE_TOPK_MAX:
+        raise ValueError(f'k must be in [1, {DICE_TOPK_MAX}]')
+    tki = np.empty((n, k), np.int32)
+    tks = np.empty((n, k), np.float64)
+    if n:
+        st = files._struct()
+        _check(load_library().dice_topk_sharded(arr, n_ctx, ctypes.byref(st), int(gather), k, _ptr(tki), _ptr(tks)))
+    return tki, tks

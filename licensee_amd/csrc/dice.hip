@@ -720,24 +720,43 @@ int dice_batch_match(dice_batch* b, double thr, void* stream) { return batch_mat
 
 int dice_batch_match_confidence(dice_batch* b, double thr, void* stream) { return batch_match(b, thr, stream, true); }
 
-static int ensure_matrix(dice_batch* b, int32_t k) {
-    dice_ctx* c = b->ctx;
-    // row stride: kind 3 writes [n][post_ld] rows of whole 128-byte lines, the others [T][n]
-    b->mat_ld = c->kind == 3 ? c->post_ld : c->T;
-    if (b->mat_cap >= b->capacity && b->mat_k >= k && b->d_mov) return DICE_OK;
-    void* ptrs[] = {b->d_mov, b->d_mscore, b->d_tki, b->d_tks};
-    for (void* p : ptrs)
-        if (p) (void)hipFree(p);
-    b->d_mov = nullptr; b->d_mscore = nullptr; b->d_tki = nullptr; b->d_tks = nullptr;
+// The [n][k] ranking buffers, all dice_batch_topk allocates.
+static int ensure_topk(dice_batch* b, int32_t k) {
+    if (b->tk_cap >= b->capacity && b->mat_k >= k && b->d_tki) return DICE_OK;
+    if (b->d_tki) (void)hipFree(b->d_tki);
+    if (b->d_tks) (void)hipFree(b->d_tks);
+    b->d_tki = nullptr; b->d_tks = nullptr;
+    b->tk_cap = 0;
     int rc;
     const int32_t kk = std::max<int32_t>(k, 1);
-    if ((rc = dalloc(&b->d_mov, (size_t)b->capacity * b->mat_ld)) ||
-        (rc = dalloc(&b->d_mscore, (size_t)b->capacity * b->mat_ld)) ||
-        (rc = dalloc(&b->d_tki, (size_t)b->capacity * kk)) || (rc = dalloc(&b->d_tks, (size_t)b->capacity * kk)))
+    if ((rc = dalloc(&b->d_tki, (size_t)b->capacity * kk)) || (rc = dalloc(&b->d_tks, (size_t)b->capacity * kk)))
         return rc;
-    b->mat_cap = b->capacity;
+    b->tk_cap = b->capacity;
     b->mat_k = kk;
     return DICE_OK;
+}
+
+static int ensure_matrix(dice_batch* b, int32_t k) {
+    dice_ctx* c = b->ctx;
+    int rc = ensure_topk(b, k);
+    if (rc) return rc;
+    // row stride: kind 3 writes [n][post_ld] rows of whole 128-byte lines, the others [T][n]
+    b->mat_ld = c->kind == 3 ? c->post_ld : c->T;
+    if (b->mat_cap >= b->capacity && b->d_mov) return DICE_OK;
+    if (b->d_mov) (void)hipFree(b->d_mov);
+    if (b->d_mscore) (void)hipFree(b->d_mscore);
+    b->d_mov = nullptr; b->d_mscore = nullptr;
+    b->mat_cap = 0;
+    if ((rc = dalloc(&b->d_mov, (size_t)b->capacity * b->mat_ld)) ||
+        (rc = dalloc(&b->d_mscore, (size_t)b->capacity * b->mat_ld)))
+        return rc;
+    b->mat_cap = b->capacity;
+    return DICE_OK;
+}
+
+int64_t dice_batch_matrix_bytes(const dice_batch* b) {
+    if (!b) return -1;
+    return b->d_mov && b->d_mscore ? b->mat_cap * (int64_t)b->mat_ld * 12 : 0;
 }
 
 int dice_batch_matrix(dice_batch* b, int32_t k, void* stream) {
@@ -745,6 +764,7 @@ int dice_batch_matrix(dice_batch* b, int32_t k, void* stream) {
     if (k < 0 || k > DICE_TOPK_MAX) return fail(DICE_E_ARG, "k out of range");
     dice_ctx* c = b->ctx;
     b->k_used = k;   // also on an empty batch: a later download with this k must be accepted
+    b->rank_mode = 1;
     if (b->n == 0) return DICE_OK;
     DeviceGuard g(c->device);
     int rc = ensure_matrix(b, k);
@@ -773,6 +793,45 @@ int dice_batch_matrix(dice_batch* b, int32_t k, void* stream) {
     return DICE_OK;
 }
 
+// The ranking of dice_batch_matrix(k) alone (dice.rb:34-41 read for its first k entries, as
+// detect.rb:96-106 does): the same kernels without the N x T rows.
+int dice_batch_topk(dice_batch* b, int32_t k, void* stream) {
+    if (k < 1 || k > DICE_TOPK_MAX) return fail(DICE_E_ARG, "k out of range");
+    if (!b) return fail(DICE_E_ARG, "NULL batch");
+    dice_ctx* c = b->ctx;
+    b->k_used = k;
+    b->rank_mode = 2;
+    if (b->n == 0) return DICE_OK;
+    DeviceGuard g(c->device);
+    int rc = ensure_topk(b, k);
+    if (rc) return rc;
+    hipStream_t s = pick_stream(c, stream);
+    b->mat_rowmajor = c->kind == 3;
+    if (c->kind == 1) {
+        rc = dice::program_launch_topk(c, b, k, s);
+        if (rc != DICE_OK) return rc;
+    } else if (c->kind == 3) {
+        rc = dice::post_launch_topk(c, b, k, s);
+        if (rc != DICE_OK) return rc;
+    } else {
+        // the reference and fallback kernel skips the rows of NULL matrix pointers
+        const int64_t n_tiles = (b->n + kWave - 1) / kWave;
+        const unsigned grid = (unsigned)((n_tiles + (kBlock / kWave) - 1) / (kBlock / kWave));
+        uint32_t* no_ov = nullptr;
+        double* no_score = nullptr;
+        if (k <= 4)
+            hipLaunchKernelGGL((dice_dense_matrix<kTT, 4>), dim3(grid), dim3(kBlock), 0, s, b->d_tiles, b->n,
+                               c->wq, c->d_tq, c->d_tc, c->T, c->tpad, b->d_wf, b->d_len, b->d_cc, k, no_ov, no_score,
+                               b->d_tki, b->d_tks);
+        else
+            hipLaunchKernelGGL((dice_dense_matrix<kTT, kTopKMax>), dim3(grid), dim3(kBlock), 0, s, b->d_tiles,
+                               b->n, c->wq, c->d_tq, c->d_tc, c->T, c->tpad, b->d_wf, b->d_len, b->d_cc, k, no_ov,
+                               no_score, b->d_tki, b->d_tks);
+    }
+    HIP_TRY(hipGetLastError());
+    return DICE_OK;
+}
+
 }  // extern "C"
 
 namespace dice {
@@ -793,22 +852,39 @@ int download_matrix_to(dice_batch* b, uint32_t* ov, double* score, int32_t* tki,
                        hipMemcpyKind kind) {
     dice_ctx* c = b->ctx;
     const int64_t n = b->n;
-    if (n && !b->d_mov) return fail(DICE_E_STATE, "dice_batch_matrix was not run");
+    if (n && (b->rank_mode == 0 || ((ov || score) && !b->d_mov)))
+        return fail(DICE_E_STATE, "dice_batch_matrix was not run");
     if (!n) return DICE_OK;
     int rc;
     if (b->mat_rowmajor) {   // already [n][ld] / [n][k]: rows of T entries at stride ld
         const size_t T = (size_t)c->T, ld = (size_t)b->mat_ld;
         if (ov) HIP_TRY(hipMemcpy2DAsync(ov, T * 4, b->d_mov, ld * 4, T * 4, (size_t)n, kind, s));
         if (score) HIP_TRY(hipMemcpy2DAsync(score, T * 8, b->d_mscore, ld * 8, T * 8, (size_t)n, kind, s));
-        if (tki && b->k_used) HIP_TRY(hipMemcpyAsync(tki, b->d_tki, (size_t)n * b->k_used * 4, kind, s));
-        if (tks && b->k_used) HIP_TRY(hipMemcpyAsync(tks, b->d_tks, (size_t)n * b->k_used * 8, kind, s));
-        HIP_TRY(hipStreamSynchronize(s));
-        return DICE_OK;
+    } else {
+        if (ov && (rc = transpose_to<uint32_t>(b, b->d_mov, c->T, n, ov, s, kind))) return rc;
+        if (score && (rc = transpose_to<double>(b, b->d_mscore, c->T, n, score, s, kind))) return rc;
     }
-    if (ov && (rc = transpose_to<uint32_t>(b, b->d_mov, c->T, n, ov, s, kind))) return rc;
-    if (score && (rc = transpose_to<double>(b, b->d_mscore, c->T, n, score, s, kind))) return rc;
-    if (tki && b->k_used && (rc = transpose_to<int32_t>(b, b->d_tki, b->k_used, n, tki, s, kind))) return rc;
-    if (tks && b->k_used && (rc = transpose_to<double>(b, b->d_tks, b->k_used, n, tks, s, kind))) return rc;
+    return download_topk_to(b, tki, tks, s, kind);
+}
+
+// The [n][k] ranking of the last dice_batch_matrix / dice_batch_topk, row-major whatever the device
+// layout is; synchronizes `s` (also with both outputs NULL).
+int download_topk_to(dice_batch* b, int32_t* tki, double* tks, hipStream_t s, hipMemcpyKind kind) {
+    const int64_t n = b->n;
+    const int32_t k = b->k_used;
+    if (!n) return DICE_OK;
+    if (k > 0 && (tki || tks)) {
+        if (!b->d_tki) return fail(DICE_E_STATE, "no ranking was run on this batch");
+        int rc;
+        if (b->mat_rowmajor) {
+            if (tki) HIP_TRY(hipMemcpyAsync(tki, b->d_tki, (size_t)n * k * 4, kind, s));
+            if (tks) HIP_TRY(hipMemcpyAsync(tks, b->d_tks, (size_t)n * k * 8, kind, s));
+        } else {
+            if (tki && (rc = transpose_to<int32_t>(b, b->d_tki, k, n, tki, s, kind))) return rc;
+            if (tks && (rc = transpose_to<double>(b, b->d_tks, k, n, tks, s, kind))) return rc;
+        }
+    }
+    HIP_TRY(hipStreamSynchronize(s));
     return DICE_OK;
 }
 
@@ -829,9 +905,23 @@ int dice_batch_download_matrix(dice_batch* b, uint32_t* ov, double* score, int32
     if ((tki || tks) && k != b->k_used)
         return fail(DICE_E_ARG, "top-k buffers are [n][k]: k must equal the last dice_batch_matrix k (" +
                                     std::to_string(b->k_used) + ")");
+    if ((ov || score) && b->rank_mode == 2)
+        return fail(DICE_E_STATE, "the last ranking was dice_batch_topk: no N x T matrix on the device");
     dice_ctx* c = b->ctx;
     DeviceGuard g(c->device);
     return dice::download_matrix_to(b, ov, score, tki, tks, pick_stream(c, stream), hipMemcpyDeviceToHost);
+}
+
+int dice_batch_download_topk(dice_batch* b, int32_t k, int32_t* tki, double* tks, void* stream) {
+    if (k < 1 || k > DICE_TOPK_MAX) return fail(DICE_E_ARG, "k out of range");
+    if (!b) return fail(DICE_E_ARG, "NULL batch");
+    if (b->rank_mode == 0) return fail(DICE_E_STATE, "no ranking was run on this batch");
+    if (k != b->k_used)
+        return fail(DICE_E_ARG, "top-k buffers are [n][k]: k must equal the k of the last ranking (" +
+                                    std::to_string(b->k_used) + ")");
+    dice_ctx* c = b->ctx;
+    DeviceGuard g(c->device);
+    return dice::download_topk_to(b, tki, tks, pick_stream(c, stream), hipMemcpyDeviceToHost);
 }
 
 int dice_batch_stream_probe(dice_batch* b, void* stream) {
@@ -983,6 +1073,7 @@ int small_batch(dice_ctx* c, dice_batch** out) {
     b->d_tki = (int32_t*)(o + L.tki);
     b->d_tks = (double*)(o + L.tks);
     b->mat_cap = kSmallFiles;
+    b->tk_cap = kSmallFiles;
     b->mat_k = DICE_TOPK_MAX;
     c->small = b;
     *out = b;
@@ -1081,6 +1172,36 @@ int small_matrix(dice_ctx* c, const dice_files* f, uint32_t* ov, double* score, 
     return DICE_OK;
 }
 
+// dice_topk for n <= kSmallFiles: the ranking areas packed for this n, one D2H
+int small_topk(dice_ctx* c, const dice_files* f, int32_t k, int32_t* tki, double* tks) {
+    DeviceGuard g(c->device);
+    dice_batch* b = nullptr;
+    int rc;
+    if ((rc = small_batch(c, &b))) return rc;
+    const SmallLayout L = small_layout(c);
+    const size_t n = (size_t)f->n_files, kk = (size_t)k;
+    const size_t o_tki = L.tki, o_tks = align_up(o_tki + n * kk * 4), o_end = o_tks + n * kk * 8;
+    char* d = (char*)b->d_out;
+    b->d_tki = (int32_t*)(d + o_tki);
+    b->d_tks = (double*)(d + o_tks);
+    if ((rc = small_upload(c, b, f, L)) || (rc = dice_batch_topk(b, k, nullptr))) return rc;
+    HIP_TRY(hipMemcpyAsync((char*)c->h_small_out + o_tki, d + o_tki, o_end - o_tki, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    const int32_t* hi = (const int32_t*)((const char*)c->h_small_out + o_tki);
+    const double* hk = (const double*)((const char*)c->h_small_out + o_tks);
+    if (b->mat_rowmajor) {
+        std::memcpy(tki, hi, n * kk * 4);
+        std::memcpy(tks, hk, n * kk * 8);
+        return DICE_OK;
+    }
+    for (size_t i = 0; i < n; ++i)   // [k][n]
+        for (size_t j = 0; j < kk; ++j) {
+            tki[i * kk + j] = hi[j * n + i];
+            tks[i * kk + j] = hk[j * n + i];
+        }
+    return DICE_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -1126,6 +1247,23 @@ int dice_similarity_matrix(dice_ctx* ctx, const dice_files* f, uint32_t* ov, dou
     if ((rc = dice_batch_upload(b, f, nullptr))) return rc;
     if ((rc = dice_batch_matrix(b, k, nullptr))) return rc;
     return dice_batch_download_matrix(b, ov, score, k, k > 0 ? tki : nullptr, k > 0 ? tks : nullptr, nullptr);
+}
+
+int dice_topk(dice_ctx* ctx, const dice_files* f, int32_t k, int32_t* tki, double* tks) {
+    if (k < 1 || k > DICE_TOPK_MAX) return fail(DICE_E_ARG, "k out of range");
+    if (!ctx || !f) return fail(DICE_E_ARG, "NULL ctx/files");
+    if (!tki || !tks) return fail(DICE_E_ARG, "top-k outputs required");
+    if (f->n_files == 0) return DICE_OK;
+    if (f->n_files < 0) return fail(DICE_E_ARG, "n_files < 0");
+    if (!f->bits || !f->wordset_size || !f->length || !f->cc_false_positive)
+        return fail(DICE_E_ARG, "NULL file arrays");
+    if (f->n_files <= kSmallFiles && !getenv_flag("DICE_NO_SMALL_CALL")) return small_topk(ctx, f, k, tki, tks);
+    dice_batch* b = nullptr;
+    int rc = dice::scratch_for(ctx, f->n_files, &b);
+    if (rc) return rc;
+    if ((rc = dice_batch_upload(b, f, nullptr))) return rc;
+    if ((rc = dice_batch_topk(b, k, nullptr))) return rc;
+    return dice_batch_download_topk(b, k, tki, tks, nullptr);
 }
 
 }  // extern "C"

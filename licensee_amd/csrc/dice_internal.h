@@ -65,6 +65,8 @@ struct dice_ctx {
     hipFunction_t prog_match = nullptr;
     hipFunction_t prog_matrix = nullptr;    // top-k <= 4
     hipFunction_t prog_matrix16 = nullptr;  // top-k <= 16
+    hipFunction_t prog_topk = nullptr;      // the ranking without the N x T rows, top-k <= 4
+    hipFunction_t prog_topk16 = nullptr;    // top-k <= 16
     hipFunction_t prog_match_mfma = nullptr;   // prog_match with the matrix-core accumulate stage (prog.mfma)
     int32_t* d_qperm = nullptr;             // sparse program tile slot -> vocabulary quad (kind 1)
     // Quads per file of the resident tile: wq (the row's quads) except for the sparse program's
@@ -127,6 +129,8 @@ int post_setup(dice_ctx* c, const dice_templates* t);
 // confidence: Dice#confidence outputs (overlap 0 and score 0.0 for a file without a match)
 int post_launch_match(dice_ctx* c, dice_batch* b, double thr, hipStream_t s, bool confidence = false);
 int post_launch_matrix(dice_ctx* c, dice_batch* b, int32_t k, hipStream_t s);
+// the same ranking into the [n][k] buffers alone: no N x T row is written (dice_batch_topk)
+int post_launch_topk(dice_ctx* c, dice_batch* b, int32_t k, hipStream_t s);
 // the deferred files idx[0 .. *pn) of a pruned match (count on the device; no host read-back)
 int post_launch_match_indexed(dice_ctx* c, dice_batch* b, double thr, const int32_t* idx, const uint32_t* pn,
                               hipStream_t s, bool confidence = false);
@@ -146,6 +150,7 @@ int download_match_to(dice_batch* b, int32_t* best, uint32_t* ov, double* score,
                       hipMemcpyKind kind);
 int download_matrix_to(dice_batch* b, uint32_t* ov, double* score, int32_t* tki, double* tks, hipStream_t s,
                        hipMemcpyKind kind);
+int download_topk_to(dice_batch* b, int32_t* tki, double* tks, hipStream_t s, hipMemcpyKind kind);
 // the Exact tables (dice_exact.hip)
 void exact_free(dice_ctx* c);
 // the device wordset tables (dice_words.hip)
@@ -169,9 +174,11 @@ struct dice_batch {
     uint32_t* d_ov = nullptr;
     double* d_score = nullptr;
     // matrix results (lazily allocated)
-    int64_t mat_cap = 0;
-    int32_t mat_k = 0;
+    int64_t mat_cap = 0;            // files the N x T buffers hold (0: not allocated)
+    int64_t tk_cap = 0;             // files the top-k buffers hold
+    int32_t mat_k = 0;              // k the top-k buffers hold
     int32_t k_used = 0;
+    int32_t rank_mode = 0;          // last ranking call: 0 none, 1 dice_batch_matrix, 2 dice_batch_topk
     bool mat_rowmajor = false;      // kind 3 writes [n][ld] / [n][k] directly (no transpose)
     int32_t mat_ld = 0;             // row stride (templates) of the row-major matrix
     uint32_t* d_mov = nullptr;      // template-major [T][capacity] (coalesced stores)

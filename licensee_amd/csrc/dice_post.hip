@@ -17,7 +17,7 @@
 //   dice_post_dense_mfma: the files' first D u64 words against the template masks as a binary
 //            matrix product on the matrix cores (FP4 block-scaled MFMA, persistent workgroups; see
 //            below), written as a row-major [n][tp] u16 matrix of partial overlaps;
-//   dice_post_narrow_{match,matrix} (one file per wave): the file's dense partials, widened,
+//   dice_post_narrow_{match,matrix,topk} (one file per wave): the file's dense partials, widened,
 //            start the wave's u32 counter row in LDS; its remaining u64 words are loaded
 //            kChunks x 64 at a time and their set bits (narrow words) are queued in a per-wave
 //            LDS list, slots assigned by a DPP wave prefix sum; walk_short gives each queued
@@ -29,7 +29,8 @@
 //            packed template constants {len | cc << 31, base | slack << 16}: the same
 //            denominator, IEEE score and strict order (score, then later key) as every other
 //            kernel, 24-bit exact compares inside the fast envelope; match mode reduces over
-//            the wave, matrix mode writes the row-major [n][T] row and a k-round top-k.
+//            the wave, matrix mode writes the row-major [n][T] row and a k-round top-k, topk
+//            mode the top-k alone.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -560,7 +561,9 @@ __device__ __forceinline__ gptr<E> uniform_ptr(E* p) {
     return (gptr<E>)(lo | (hi << 32));
 }
 
-template <bool kMatrix, int TJ, bool FAST>
+// kRows (matrix mode): the file's N x T row is stored. Without it (dice_post_narrow_topk) the row
+// pointers and stores do not exist and only the [n][k] ranking leaves the wave.
+template <bool kMatrix, bool kRows, int TJ, bool FAST>
 __device__ __forceinline__ void score_file_t(uint32_t* crow32, const uint2* tcs, int32_t T, int32_t ld, int64_t file, uint32_t wf,
                                              int32_t lf, bool cc, double thr, int32_t* __restrict__ best_out,
                                              uint32_t* __restrict__ ov_out, double* __restrict__ score_out, int32_t k,
@@ -576,11 +579,11 @@ __device__ __forceinline__ void score_file_t(uint32_t* crow32, const uint2* tcs,
     gptr<uint32_t> orow = nullptr;
     gptr<double> srow = nullptr;
     uint32_t lo = (uint32_t)lane;
-    if (kMatrix) {
+    if (kRows) {
         orow = uniform_ptr(mov + file * ld);
         srow = uniform_ptr(msc + file * ld);
-        asm volatile("" : "+v"(lo));
     }
+    if (kMatrix) asm volatile("" : "+v"(lo));
     constexpr int kUnroll = kMatrix ? 10 : 2;
     DICE_UNROLL(kUnroll)
     for (int j = 0; j < TJ; ++j) {
@@ -604,7 +607,7 @@ __device__ __forceinline__ void score_file_t(uint32_t* crow32, const uint2* tcs,
             } else {
                 lane_best<FAST>(crow32, tcs, t, wf, lf, cc, bi, bo, bd, ov, den);
             }
-            if (kMatrix) {
+            if (kRows) {
                 __builtin_nontemporal_store(ov, orow + t);
                 __builtin_nontemporal_store(dice_score(ov, den), srow + t);
             }
@@ -664,7 +667,7 @@ __device__ __forceinline__ void score_file_t(uint32_t* crow32, const uint2* tcs,
     }
 }
 
-template <bool kMatrix, int TJ>
+template <bool kMatrix, bool kRows, int TJ>
 __device__ __forceinline__ void score_file(uint32_t* crow32, const uint2* tcs, int32_t T, int32_t ld, int64_t file, uint32_t wf,
                                            int32_t lf, bool cc, bool corpus_fast, double thr, int32_t* __restrict__ best_out,
                                            uint32_t* __restrict__ ov_out, double* __restrict__ score_out, int32_t k,
@@ -672,10 +675,10 @@ __device__ __forceinline__ void score_file(uint32_t* crow32, const uint2* tcs, i
                                            double* __restrict__ tks, int lane) {
     // file inside the fast envelope (wave-uniform): 24-bit exact compares
     if (corpus_fast && wf < (1u << 20) && lf >= 0 && lf < (1 << 21))
-        score_file_t<kMatrix, TJ, true>(crow32, tcs, T, ld, file, wf, lf, cc, thr, best_out, ov_out, score_out, k, mov,
+        score_file_t<kMatrix, kRows, TJ, true>(crow32, tcs, T, ld, file, wf, lf, cc, thr, best_out, ov_out, score_out, k, mov,
                                         msc, tki, tks, lane);
     else
-        score_file_t<kMatrix, TJ, false>(crow32, tcs, T, ld, file, wf, lf, cc, thr, best_out, ov_out, score_out, k, mov,
+        score_file_t<kMatrix, kRows, TJ, false>(crow32, tcs, T, ld, file, wf, lf, cc, thr, best_out, ov_out, score_out, k, mov,
                                          msc, tki, tks, lane);
 }
 
@@ -689,7 +692,7 @@ constexpr int pairs_per_lane() { return (TPMAX / 2 + kWave - 1) / kWave; }   // 
 // mode prefetches the next file's partials while it scores this one (its loads do not depend on
 // the walk); the matrix kernel loads them at the file's start (file_postings LATE). The match
 // kernel's LDS footprint (~77 KiB) and <= 64 VGPRs leave room for two workgroups per CU.
-template <bool kMatrix, int TPMAX>
+template <bool kMatrix, int TPMAX, bool kRows = kMatrix>
 __device__ __forceinline__ void post_narrow_body(
     const uint64_t* __restrict__ rows, int64_t n, int32_t w64, int32_t D, int32_t T, int32_t tp,
     const uint16_t* __restrict__ part16, const uint16_t* __restrict__ prow, const uint16_t* __restrict__ plong,
@@ -780,7 +783,7 @@ __device__ __forceinline__ void post_narrow_body(
         if (kEarly && fi + kNarrowWaves < nt) load_partials<kPJ, false>(part16, pos + kNarrowWaves, tpf, lane, pre);
 
         if (POST_DIAG & 8) continue;
-        score_file<kMatrix, kTJ>(crow32, tcs, Tf, ldf, file, wf, lf, cc, corpus_fast, thr, best_out, ov_out, score_out,
+        score_file<kMatrix, kRows, kTJ>(crow32, tcs, Tf, ldf, file, wf, lf, cc, corpus_fast, thr, best_out, ov_out, score_out,
                                  k, mov, msc, tki, tks, lanef);
     }
     }
@@ -806,6 +809,14 @@ template <int TPMAX>
 __global__ __launch_bounds__(kNarrowWavesMatrix * kWave) __attribute__((amdgpu_waves_per_eu(kNarrowOccMatrix, kNarrowOccMatrix))) void dice_post_narrow_matrix(POST_NARROW_ARGS) {
     post_narrow_body<true, TPMAX>(rows, n, w64, D, T, tp, part16, prow, plong, tc, wfp, lenp, ccp, thr, best_out, ov_out,
                                   score_out, k, mov, msc, tki, tks, corpus_fast, idx, pn, ld);
+}
+
+// The matrix kernel without the row stores: walk, two-best-per-lane ranking and k rounds unchanged,
+// mov / msc never read (dice_batch_topk).
+template <int TPMAX>
+__global__ __launch_bounds__(kNarrowWavesMatrix * kWave) __attribute__((amdgpu_waves_per_eu(kNarrowOccMatrix, kNarrowOccMatrix))) void dice_post_narrow_topk(POST_NARROW_ARGS) {
+    post_narrow_body<true, TPMAX, false>(rows, n, w64, D, T, tp, part16, prow, plong, tc, wfp, lenp, ccp, thr, best_out,
+                                         ov_out, score_out, k, mov, msc, tki, tks, corpus_fast, idx, pn, ld);
 }
 
 // ---- host side ---------------------------------------------------------------------------
@@ -979,7 +990,7 @@ int post_reserve(dice_ctx* c, dice_batch* b) {
 
 // idx/pn (match mode only): score the *pn files idx[0..*pn) of the batch (the pruned match's
 // deferred files) on persistent grids; nothing is read back on the host.
-template <bool kMatrix>
+template <bool kMatrix, bool kRows = kMatrix>
 static int launch(dice_ctx* c, dice_batch* b, double thr, int32_t k, hipStream_t s, const int32_t* idx = nullptr,
                   const uint32_t* pn = nullptr) {
     int rc = post_reserve(c, b);
@@ -1003,13 +1014,17 @@ static int launch(dice_ctx* c, dice_batch* b, double thr, int32_t k, hipStream_t
             default: launch_dense<20>(c, b, s, groups, idx, pn); break;
         }
     }
-    auto kern = c->post_tp <= 608 ? (kMatrix ? dice_post_narrow_matrix<608> : dice_post_narrow_match<608>)
-                                  : (kMatrix ? dice_post_narrow_matrix<kPostMaxTpad> : dice_post_narrow_match<kPostMaxTpad>);
+    auto kern = c->post_tp <= 608
+                    ? (!kMatrix ? dice_post_narrow_match<608> : kRows ? dice_post_narrow_matrix<608> : dice_post_narrow_topk<608>)
+                    : (!kMatrix ? dice_post_narrow_match<kPostMaxTpad>
+                       : kRows  ? dice_post_narrow_matrix<kPostMaxTpad>
+                                : dice_post_narrow_topk<kPostMaxTpad>);
     hipLaunchKernelGGL(kern, dim3((unsigned)groups), dim3(kNarrowWaves * kWave), 0, s,
                        (const uint64_t*)b->d_rows, b->n, c->w64, c->post_dense, c->T, c->post_tp,
                        part16, (const uint16_t*)c->d_prow, (const uint16_t*)c->d_povf,
                        (const uint2*)c->d_ptc, b->d_wf, b->d_len, b->d_cc, thr, b->d_best, b->d_ov, b->d_score, k,
-                       b->d_mov, b->d_mscore, k > 0 ? b->d_tki : nullptr, b->d_tks, c->post_fast, idx,
+                       kRows ? b->d_mov : nullptr, kRows ? b->d_mscore : nullptr, k > 0 ? b->d_tki : nullptr, b->d_tks,
+                       c->post_fast, idx,
                        pn, c->post_ld);
     return hipGetLastError() == hipSuccess ? DICE_OK : fail(DICE_E_DEVICE, "dice_post kernels launch failed");
 }
@@ -1028,5 +1043,7 @@ int post_launch_matrix(dice_ctx* c, dice_batch* b, int32_t k, hipStream_t s) {
     // any k <= 16: one candidate per lane, k wave argmax rounds (score_file_t)
     return launch<true>(c, b, 0.0, k, s);
 }
+
+int post_launch_topk(dice_ctx* c, dice_batch* b, int32_t k, hipStream_t s) { return launch<true, false>(c, b, 0.0, k, s); }
 
 }  // namespace dice

@@ -147,7 +147,9 @@ int program_setup(dice_ctx* c, const dice_templates* t) {
     if (hipModuleLoadData(&c->module, code.data()) != hipSuccess) return fail(DICE_E_DEVICE, "hipModuleLoadData failed");
     auto get = [&](hipFunction_t* fn, const char* name) { return hipModuleGetFunction(fn, c->module, name) == hipSuccess; };
     if (!get(&c->prog_match, "dice_prog_match") || !get(&c->prog_matrix, "dice_prog_matrix4") ||
-        !get(&c->prog_matrix16, "dice_prog_matrix16") || (p.mfma && !get(&c->prog_match_mfma, "dice_prog_match_mfma")))
+        !get(&c->prog_matrix16, "dice_prog_matrix16") || !get(&c->prog_topk, "dice_prog_topk4") ||
+        !get(&c->prog_topk16, "dice_prog_topk16") ||
+        (p.mfma && !get(&c->prog_match_mfma, "dice_prog_match_mfma")))
         return fail(DICE_E_DEVICE, "hipModuleGetFunction failed");
     if (p.sched.qperm.size() != (size_t)p.wq) return fail(DICE_E_STATE, "program tile permutation size");
     if (p.opts.compact) {   // the module's own dice_pack_compact fills the tile
@@ -200,6 +202,21 @@ int program_launch_matrix(dice_ctx* c, dice_batch* b, int32_t k, hipStream_t s) 
     hipFunction_t fn = k <= 4 ? c->prog_matrix : c->prog_matrix16;
     if (hipModuleLaunchKernel(fn, grid, 1, 1, 64 * wpb, 1, 1, 0, s, args, nullptr) != hipSuccess)
         return fail(DICE_E_DEVICE, "launch dice_prog_matrix failed");
+    return DICE_OK;
+}
+
+int program_launch_topk(dice_ctx* c, dice_batch* b, int32_t k, hipStream_t s) {
+    const int64_t n_tiles = (b->n + 63) / 64;
+    const int32_t wpb = kProgramWaves;
+    const unsigned grid = (unsigned)((n_tiles + wpb - 1) / wpb);
+    int64_t n = b->n;
+    int32_t kk = k;
+    void* args[] = {&b->d_tiles, &n, &b->d_wf, &b->d_len, &b->d_cc, &kk, &b->d_tki, &b->d_tks};
+    // the VALU program under every DICE_PROG_MATCH: the matrix-core stage measured slower here too
+    // (DESIGN.md Appendix B), the k sorted slots' offers bound the kernel, not the accumulation
+    hipFunction_t fn = k <= 4 ? c->prog_topk : c->prog_topk16;
+    if (hipModuleLaunchKernel(fn, grid, 1, 1, 64 * wpb, 1, 1, 0, s, args, nullptr) != hipSuccess)
+        return fail(DICE_E_DEVICE, "launch dice_prog_topk failed");
     return DICE_OK;
 }
 

@@ -668,11 +668,21 @@ extern "C" __global__ __launch_bounds__(64 * WPB) void dice_prog_match(
 }
 )HIP";
 
-// Matrix kernel template: KM is the compile-time top-k slot count (4 or 16).
+// Matrix kernel template: KM is the compile-time top-k slot count (4 or 16). MROWS 1 is the matrix
+// kernel (dice_prog_matrix*: every template's overlap and score stored, then the ranking); MROWS 0 is
+// the same text without the row pointers, their arguments and the row stores (dice_prog_topk*:
+// the ranking alone, dice.rb:34-41 read for its first k entries as detect.rb:96-106 does).
 const char* kMatrixKernel = R"HIP(
+#if MROWS
+#define MROW_ARGS u32* __restrict__ ov_out, double* __restrict__ score_out,
+#define MROW_STORE(T) if (valid) { if (orow) MSTORE(orow + (i64)(T) * n, a); if (srow) MSTORE(srow + (i64)(T) * n, sc(a, d)); }
+#else
+#define MROW_ARGS
+#define MROW_STORE(T)
+#endif
 extern "C" __global__ __launch_bounds__(64 * WPB) void KNAME(
     const uint4* __restrict__ files, i64 n, const u32* __restrict__ wfp, const i32* __restrict__ lenp,
-    const unsigned char* __restrict__ ccp, i32 k, u32* __restrict__ ov_out, double* __restrict__ score_out,
+    const unsigned char* __restrict__ ccp, i32 k, MROW_ARGS
     i32* __restrict__ topk_idx, double* __restrict__ topk_score) {
     const int lane = threadIdx.x & 63;
     const i64 tile = (i64)blockIdx.x * WPB + (threadIdx.x >> 6);
@@ -688,9 +698,11 @@ extern "C" __global__ __launch_bounds__(64 * WPB) void KNAME(
     i32 ti[KM]; u32 to[KM]; i32 td[KM];
 #pragma unroll
     for (int j = 0; j < KM; ++j) { ti[j] = -1; to[j] = 0; td[j] = 1; }
+#if MROWS
     // template-major [NT][n] outputs: for a fixed template the 64 lanes store contiguously
     u32* orow = ov_out ? ov_out + file : nullptr;
     double* srow = score_out ? score_out + file : nullptr;
+#endif
     if (__all(fast)) {
         MATRIX_BODY(true)
     } else {
@@ -706,15 +718,18 @@ extern "C" __global__ __launch_bounds__(64 * WPB) void KNAME(
         }
     }
 }
+#undef MROW_ARGS
+#undef MROW_STORE
 )HIP";
 
-// Per-template matrix epilogue: store the row entry, then rank-and-shift insertion into the
-// KM sorted slots (p = slots that strictly outrank the candidate; a later template goes
-// before equal-scored earlier ones, dice.rb:39). Branch-free selects only.
+// Per-template matrix epilogue: store the row entry (MROW_STORE, empty in the top-k kernels), then
+// rank-and-shift insertion into the KM sorted slots (p = slots that strictly outrank the
+// candidate; a later template goes before equal-scored earlier ones, dice.rb:39). Branch-free
+// selects only.
 const char* kMatrixOffer = R"HIP(
 #define MOFFER(T, CCF)                                                                  \
     {                                                                                   \
-        if (valid) { if (orow) MSTORE(orow + (i64)(T) * n, a); if (srow) MSTORE(srow + (i64)(T) * n, sc(a, d)); } \
+        MROW_STORE(T)                                                                   \
         if (!((CCF) && cc)) {                                                           \
             int p = 0;                                                                  \
             _Pragma("unroll") for (int j = 0; j < KM; ++j)                              \
@@ -750,7 +765,8 @@ const char* kMatrixOffer = R"HIP(
 // from LDS nor multiplied, and a K-step that is live in no block is not widened. A workgroup of MWK = 12 waves walks a contiguous share of the tiles,
 // wave w taking every MWK-th; the next tile's quads are requested as this tile's K-steps retire
 // them. Match mode only: the matrix kernels, bound by their 600 B per file of stores, measured
-// 17% slower with the stage and keep the VALU program.
+// 17% slower with the stage and keep the VALU program; so do the top-k
+// kernels, which store nothing per template but are bound by the slot offers (3% slower, B.6).
 const char* kMfmaPrelude = R"HIP(
 typedef int v8i __attribute__((ext_vector_type(8)));
 typedef float v16f __attribute__((ext_vector_type(16)));
@@ -1241,9 +1257,11 @@ std::string emit_program(const dice_templates* t, const Program& p) {
       << "#undef ACC_INIT\n#define ACC_INIT(i) 0u\n";
     s << kMatrixOffer;
     emit_macro(s, "MATRIX_BODY(FASTV_) { constexpr bool FASTV = FASTV_;", matrix_body + "}");
-    for (int km : {4, 16}) {
-        s << "#define KM " << km << "\n#define KNAME dice_prog_matrix" << km << "\n" << kMatrixKernel
-          << "#undef KM\n#undef KNAME\n";
+    for (int rows : {1, 0}) {
+        for (int km : {4, 16}) {
+            s << "#define KM " << km << "\n#define MROWS " << rows << "\n#define KNAME dice_prog_"
+              << (rows ? "matrix" : "topk") << km << "\n" << kMatrixKernel << "#undef KM\n#undef MROWS\n#undef KNAME\n";
+        }
     }
     if (p.mfma) {
         // the match kernel with the matrix-core accumulate stage, device compile only

@@ -304,6 +304,42 @@ int dice_similarity_matrix_sharded(dice_ctx* const* ctxs, int32_t n_ctx, const d
     return rc;
 }
 
+int dice_topk_sharded(dice_ctx* const* ctxs, int32_t n_ctx, const dice_files* f, int32_t gather, int32_t k,
+                      int32_t* tki, double* tks) {
+    if (k < 1 || k > DICE_TOPK_MAX) return fail(DICE_E_ARG, "k out of range");
+    int rc = check_ctxs(ctxs, n_ctx, f, gather);
+    if (rc) return rc;
+    if (!tki || !tks) return fail(DICE_E_ARG, "top-k outputs required");
+    const int64_t n = f->n_files;
+    if (n == 0) return DICE_OK;
+    if (!f->bits || !f->wordset_size || !f->length || !f->cc_false_positive) return fail(DICE_E_ARG, "NULL file arrays");
+    const int32_t w64 = ctxs[0]->w64;
+    // device gather layout (row-major, as the ABI): top-k index [n][k] i32 | top-k score [n][k] f64
+    const size_t b_ki = (size_t)n * k * 4, b_ks = (size_t)n * k * 8;
+    char* dev = nullptr;
+    g_last_gather_peer = -1;
+    if (gather == DICE_GATHER_DEVICE) {
+        if ((rc = gather_alloc(ctxs[0], b_ki + b_ks, (void**)&dev))) return rc;
+        prepare_device_gather(ctxs, n_ctx);
+    }
+    rc = run_shards(ctxs, n_ctx, n, [&](int32_t i, Shard& s) {
+        dice_ctx* c = ctxs[i];
+        dice_batch* b = nullptr;
+        int r = dice::scratch_for(c, s.hi - s.lo, &b);
+        if (r) return r;
+        const dice_files part = slice(f, s.lo, s.hi, w64);
+        if ((r = upload_shard(c, b, &part)) || (r = dice_batch_topk(b, k, nullptr))) return r;
+        const size_t lo = (size_t)s.lo;
+        if (dev)
+            return dice::download_topk_to(b, (int32_t*)dev + lo * k, (double*)(dev + b_ki) + lo * k, c->stream,
+                                          hipMemcpyDefault);
+        return dice::download_topk_to(b, tki + lo * k, tks + lo * k, c->stream, hipMemcpyDeviceToHost);
+    });
+    if (rc == DICE_OK && dev) rc = gather_d2h(ctxs[0], {{tki, b_ki}, {tks, b_ks}}, dev);
+    if (dev) (void)hipFree(dev);
+    return rc;
+}
+
 int32_t dice_last_gather_peer(void) { return g_last_gather_peer; }
 
 }  // extern "C"

@@ -50,10 +50,12 @@ class DiceEngine:
 
     def closest_files(self, files: Sequence, k: int = 3) -> List[List[Tuple[License, float]]]:
         """Batched ``licenses_by_similarity(f)[0...k]`` (detect.rb:55-64, "Closest non-matching
-        licenses") from the matrix kernel's top-k with the CC filter off."""
+        licenses") from the top-k kernels (``dice_topk``: no [n][T] matrix) with the CC filter off."""
         fb = self.intern(files)
         fb.cc_false_positive[:] = 0
-        _, _, idx, score = self.scorer.matrix(fb, k)
+        if k < 1:
+            return [[] for _ in range(fb.n)]
+        idx, score = self.scorer.topk(fb, k)
         return [[(self.templates[t], s) for t, s in zip(ri.tolist(), rs.tolist()) if t >= 0]
                 for ri, rs in zip(idx, score)]
 
