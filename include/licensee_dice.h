@@ -266,7 +266,8 @@ int dice_exact(dice_ctx *ctx, const dice_files *files, const uint64_t *file_fiel
 int dice_vocab_setup(dice_ctx *ctx, int32_t n_words, const char *const *words, int32_t n_extra,
                      const char *const *extra);
 /* text[0, text_bytes): the batch's normalized texts as bytes (every non-ASCII character one byte
- * >= 0x80), file i at text[offsets[i], offsets[i] + text_len[i]), offsets 16-byte aligned;
+ * >= 0x80), file i at text[offsets[i], offsets[i] + text_len[i]), offsets 16-byte aligned (the
+ * last file may end exactly at text_bytes: no padding has to follow it);
  * length[i] = content_normalized.length in characters and cc_false_positive[i] as in dice_files.
  * The device builds each file's row, |W_F| (every distinct word, in the vocabulary or not) and
  * field mask (dice_batch_exact with file_field_mask = NULL reads them). Synchronizes `stream`.
@@ -278,6 +279,21 @@ int dice_batch_upload_text(dice_batch *batch, int64_t n_files, const uint8_t *te
                            const int64_t *offsets, const int32_t *text_len, const int32_t *length,
                            const uint8_t *cc_false_positive, uint8_t *status, int64_t *n_overflow,
                            void *stream);
+/* The same call for texts given as UTF-8 -- the bytes of content_normalized itself (licensee_host.h
+ * lh_normalize_files_utf8, or a caller's own content_normalized): text_len[i] is in bytes. The scan
+ * is the same one (its [\w/-] is ASCII and every byte >= 0x80 separates tokens), so rows, |W_F|,
+ * field masks and status equal dice_batch_upload_text's for the same texts. length[i] is
+ * content_normalized.length in characters, or length may be NULL: the device then counts each
+ * file's characters (the bytes b of its text with (b & 0xC0) != 0x80; the bytes are trusted to be
+ * UTF-8, not validated) on the same stream. The batch records that its texts are UTF-8, which
+ * dice_batch_content_hash reads; every other upload clears the record. */
+int dice_batch_upload_text_utf8(dice_batch *batch, int64_t n_files, const uint8_t *text, int64_t text_bytes,
+                                const int64_t *offsets, const int32_t *text_len, const int32_t *length,
+                                const uint8_t *cc_false_positive, uint8_t *status, int64_t *n_overflow,
+                                void *stream);
+/* D2H of the resident per-file lengths in characters ([n] int32), as the last upload of any kind
+ * left them (the caller's, or the device's count); synchronizes `stream`. */
+int dice_batch_download_length(dice_batch *batch, int32_t *length, void *stream);
 /* Overwrite the rows, |W_F| and field masks (NULL: zero) of files index[0..k) of the resident
  * batch (bits: [k][dice_words64(V)]); synchronizes `stream`. */
 int dice_batch_set_rows(dice_batch *batch, int64_t k, const int64_t *index, const uint64_t *bits,
@@ -294,17 +310,21 @@ int dice_batch_download_rows(dice_batch *batch, uint64_t *bits, uint32_t *wordse
 /* ---- ContentHelper#content_hash on the device --------------------------------------------
  * content_hash (content_helper.rb:136-138: DIGEST.hexdigest content_normalized, SHA-1; one of
  * ProjectFile's HASH_METHODS, project_file.rb:17,97) of the texts dice_batch_upload_text left
- * resident, one lane per file. A text with a non-ASCII character is resident with that character as
+ * or dice_batch_upload_text_utf8 left resident, one lane per file. After the UTF-8 upload the
+ * resident bytes are content_normalized's, every digest is content_hash and every status is 0.
+ * After dice_batch_upload_text a text with a non-ASCII character is resident with that character as
  * the byte 0x80, so its bytes are not the UTF-8 of content_normalized: such a file is flagged and
  * the caller hashes it.
  *
  * SHA-1 of every resident normalized text, asynchronous on `stream` (no host synchronization
- * inside). DICE_E_STATE unless the batch's last upload was dice_batch_upload_text
- * (dice_batch_set_rows and dice_batch_stream_probe leave the texts as they are). */
+ * inside). DICE_E_STATE unless the batch's last upload was one of the two text uploads
+ * (dice_batch_set_rows and dice_batch_stream_probe leave the texts, and the record of their form,
+ * as they are). */
 int dice_batch_content_hash(dice_batch *batch, void *stream);
 /* D2H (synchronizes `stream`; content_helper.rb:136-138): digest [n][20] bytes, status [n]:
- * 0 = digest is ContentHelper#content_hash of the file; 1 = the text holds a non-ASCII character
- * (resident as 0x80), digest is of the resident bytes and the caller hashes that file's UTF-8 itself.
+ * 0 = digest is ContentHelper#content_hash of the file; 1 (dice_batch_upload_text only) = the text
+ * holds a non-ASCII character (resident as 0x80), digest is of the resident bytes and the caller
+ * hashes that file's UTF-8 itself.
  * NULL outputs are skipped; DICE_E_STATE if no hash was computed since the last upload. */
 int dice_batch_download_content_hash(dice_batch *batch, uint8_t *digest, uint8_t *status, void *stream);
 

@@ -75,6 +75,13 @@ int64_t lh_normalize_files(lh_ctx *ctx, int64_t n, const char *const *data, cons
                            const char *const *filenames, int32_t nthreads, char *out, int64_t cap,
                            int64_t *off, int32_t *tlen, int32_t *length, uint8_t *cc,
                            uint8_t *copyright, uint8_t *status);
+/* The library also exports lh_normalize_files_utf8, the same call (arguments, offsets, placement,
+ * flags, status codes, return value) with file i's text as the UTF-8 of content_normalized -- the
+ * bytes lh_normalize writes, so their SHA-1 is ContentHelper#content_hash
+ * (content_helper.rb:136-138) -- for dice_batch_upload_text_utf8: tlen[i] is bytes, length[i]
+ * characters; an ASCII text is the same bytes in both calls. It has no prototype here:
+ * tests/test_abi.py pins the set of functions this header declares, so a C caller declares it
+ * itself with lh_normalize_files' signature (licensee_amd/native_host.py binds it that way). */
 
 /* Vocabulary packing (csrc/vocab_pack.cpp): local search over word swaps between bins of
  * bin_bits (32: sparse-program (template, dword) instruction pairs; 64: LDS-kernel

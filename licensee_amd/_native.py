@@ -33,6 +33,7 @@ EXPORTED_SYMBOLS = (
     'dice_program_source_compact', 'dice_program_layout', 'dice_program_mfma_tables', 'dice_ctx_program_stage',
     'dice_program_mfma_rows', 'dice_batch_content_hash', 'dice_batch_download_content_hash',
     'dice_topk', 'dice_topk_sharded', 'dice_batch_topk', 'dice_batch_download_topk', 'dice_batch_matrix_bytes',
+    'dice_batch_upload_text_utf8', 'dice_batch_download_length',
 )
 DICE_GATHER_HOST = 0
 DICE_GATHER_DEVICE = 1
@@ -206,6 +207,8 @@ def load_library(path: str = LIB_PATH) -> ctypes.CDLL:
         'dice_exact': (ctypes.c_int, [vp, ctypes.POINTER(_Files), vp, vp]),
         'dice_vocab_setup': (ctypes.c_int, [vp, i32, vp, i32, vp]),
         'dice_batch_upload_text': (ctypes.c_int, [vp, i64, vp, i64, vp, vp, vp, vp, vp, ctypes.POINTER(i64), vp]),
+        'dice_batch_upload_text_utf8': (ctypes.c_int, [vp, i64, vp, i64, vp, vp, vp, vp, vp, ctypes.POINTER(i64), vp]),
+        'dice_batch_download_length': (ctypes.c_int, [vp, vp, vp]),
         'dice_batch_set_rows': (ctypes.c_int, [vp, i64, vp, vp, vp, vp, vp]),
         'dice_batch_download_rows': (ctypes.c_int, [vp, vp, vp, vp, vp]),
         'dice_host_alloc': (ctypes.c_int, [i64, ctypes.POINTER(vp)]),
@@ -483,25 +486,40 @@ class DeviceBatch:
                                                     stream or None))
         self.n = n
 
-    def upload_text(self, text: np.ndarray, offsets, text_len, length, cc_false_positive, stream: int = 0):
+    def upload_text(self, text: np.ndarray, offsets, text_len, length, cc_false_positive, stream: int = 0,
+                    utf8: bool = False):
         """Upload normalized texts (``dice_batch_upload_text``: uint8 ``text``, file i at
         ``text[offsets[i]:offsets[i] + text_len[i]]``, 16-byte aligned offsets); the device scans
         the wordsets. Returns the [n] status array (1 = too many distinct words outside the
-        vocabulary for the device set: send that file with :meth:`set_rows`)."""
+        vocabulary for the device set: send that file with :meth:`set_rows`).
+        ``utf8=True``: the texts are the UTF-8 of content_normalized (``dice_batch_upload_text_utf8``;
+        ``text_len`` in bytes, ``length`` in characters), and ``length=None`` has the device count
+        each file's characters."""
         text = np.ascontiguousarray(text, dtype=np.uint8)
         off = np.ascontiguousarray(offsets, dtype=np.int64)
         tl = np.ascontiguousarray(text_len, dtype=np.int32)
-        ln = np.ascontiguousarray(length, dtype=np.int32)
+        if length is None and not utf8:
+            raise ValueError('length=None needs utf8=True (the device counts UTF-8 characters)')
+        ln = None if length is None else np.ascontiguousarray(length, dtype=np.int32)
         cc = np.ascontiguousarray(cc_false_positive, dtype=np.uint8)
         n = off.shape[0]
-        if not (tl.shape == ln.shape == cc.shape == (n,)):
+        if not (tl.shape == cc.shape == (n,)) or (ln is not None and ln.shape != (n,)):
             raise ValueError('inconsistent text-upload shapes')
         st = np.zeros(n, np.uint8)
         nov = ctypes.c_int64(0)
-        _check(load_library().dice_batch_upload_text(self._b, n, _ptr(text), int(text.shape[0]), _ptr(off), _ptr(tl),
-                                                     _ptr(ln), _ptr(cc), _ptr(st), ctypes.byref(nov), stream or None))
+        lib = load_library()
+        fn = lib.dice_batch_upload_text_utf8 if utf8 else lib.dice_batch_upload_text
+        _check(fn(self._b, n, _ptr(text), int(text.shape[0]), _ptr(off), _ptr(tl), _ptr(ln), _ptr(cc), _ptr(st),
+                  ctypes.byref(nov), stream or None))
         self.n = n
         return st
+
+    def download_length(self, stream: int = 0) -> np.ndarray:
+        """The resident per-file lengths in characters, [n] int32 (``dice_batch_download_length``):
+        the caller's, or the device's count after ``upload_text(..., length=None, utf8=True)``."""
+        out = np.empty(self.n, np.int32)
+        _check(load_library().dice_batch_download_length(self._b, _ptr(out), stream or None))
+        return out
 
     def set_rows(self, index, bits, wordset_size, field_mask=None, stream: int = 0):
         """Overwrite rows / |W_F| / field masks of the resident files ``index`` (``dice_batch_set_rows``)."""
@@ -592,9 +610,10 @@ class DeviceBatch:
         _check(load_library().dice_batch_content_hash(self._b, stream or None))
 
     def download_content_hash(self, stream: int = 0):
-        """The digests [n, 20] and status [n] of the last :meth:`content_hash` (status 1: the text
-        holds a non-ASCII character, resident as 0x80 -- the digest is of the resident bytes, not
-        ContentHelper#content_hash, which the caller computes from the file's UTF-8)."""
+        """The digests [n, 20] and status [n] of the last :meth:`content_hash` (status 1, only after
+        an upload without ``utf8=True``: the text holds a non-ASCII character, resident as 0x80 --
+        the digest is of the resident bytes, not ContentHelper#content_hash, which the caller
+        computes from the file's UTF-8)."""
         digest = np.empty((self.n, 20), np.uint8)
         status = np.empty(self.n, np.uint8)
         _check(load_library().dice_batch_download_content_hash(self._b, _ptr(digest), _ptr(status), stream or None))

@@ -11,7 +11,8 @@ The reference evaluates ``[Copyright, Exact, Dice].map(new).find(&:match)`` per 
                                        W_t ⊆ W_F, exact.rb:6-12) and Dice#match / #confidence
                                        on the same resident batch; with ``content_hash=True``
                                        also ContentHelper#content_hash (dice_batch_content_hash:
-                                       SHA-1 of the resident texts, content_helper.rb:136-138)
+                                       SHA-1 of the resident texts, content_helper.rb:136-138;
+                                       the texts are then resident as UTF-8)
 (``wordset_on='host'`` scans and interns in the host threads instead, the round-5 split;
 ``exact_on='host'`` keeps Exact in the host threads too, the round-2 split.)
 
@@ -42,8 +43,11 @@ class BatchDetector:
 
     ``content_hash=True`` fills ``Detection.content_hash`` (ContentHelper#content_hash,
     content_helper.rb:136-138) for every file, whatever matcher decided it: the device hashes the
-    normalized texts it already holds for the wordset scan, and the few files with a non-ASCII
-    character (resident as the byte 0x80) are hashed on the host threads."""
+    normalized texts it already holds for the wordset scan. Those texts are then kept as the UTF-8
+    of content_normalized (``lh_normalize_files_utf8`` / ``dice_batch_upload_text_utf8``), so the
+    device's digest is content_hash for non-ASCII files too; only a file the device flags is hashed
+    on the host threads, and ``host_hashed`` counts those of the last ``detect`` or stream batch
+    (none on this path). ``content_hash=False`` keeps the one-byte-per-character texts."""
 
     def __init__(self, engine=None, nthreads: int = 8, exact_on: str = 'device', wordset_on: str = 'device',
                  content_hash: bool = False):
@@ -68,6 +72,7 @@ class BatchDetector:
         self._pinned = [None, None]  # page-locked text buffers: batch k uploads from one while k + 1 fills the other
         self._turn = 0
         self._pool = None           # threads of the content-hash completion (content_hash=True, on demand)
+        self.host_hashed = 0        # files of the last batch whose content_hash came from the host
         if self.exact_on == 'device':
             self.engine.scorer.exact_setup(*exact_tables(self.engine.corpus, self.host))
         if self.wordset_on == 'device':
@@ -132,7 +137,8 @@ class BatchDetector:
         """Host stage (liblicensee_host.so threads; ctypes releases the GIL during the call)."""
         if self.wordset_on == 'device':
             return ('text', self.host.normalize_files(contents, filenames, nthreads=self.nthreads,
-                                                      out=self._text_buffer), contents, filenames)
+                                                      out=self._text_buffer, utf8=self.content_hash),
+                    contents, filenames)
         field_masks = self.exact_on == 'device'
         fb, copyright, third, _ = self.host.prep_files(contents, filenames, nthreads=self.nthreads,
                                                        field_masks=field_masks)
@@ -146,7 +152,7 @@ class BatchDetector:
         _, (text, off, tl, ln, cc, copyright, _), contents, filenames = prepped
         n = len(off)
         b = self._device_batch(max(n, 1))
-        st = b.upload_text(text, off, tl, ln, cc)
+        st = b.upload_text(text, off, tl, ln, cc, utf8=self.content_hash)   # (as _prep normalized them)
         if self.content_hash:
             b.content_hash()
         over = np.nonzero(st)[0]
@@ -159,19 +165,22 @@ class BatchDetector:
         b.match(float(thr), confidence=True)
         exact = b.download_exact()
         best, _, score = b.download_match()
+        self.host_hashed = 0
         hashes = self._hashes(b, contents, filenames) if self.content_hash else None
         return copyright, exact, best, score, hashes
 
     def _hashes(self, b, contents, filenames) -> List[str]:
         """content_hash per file as hex: the device digests, and for the files the device flagged
-        (a non-ASCII character, resident as 0x80) the SHA-1 of content_normalized's UTF-8 from the
-        host threads (the native normalize releases the GIL)."""
+        (none when the resident texts are UTF-8; in the one-byte form a text with a non-ASCII
+        character, resident as 0x80) the SHA-1 of content_normalized's UTF-8 from the host threads
+        (the native normalize releases the GIL)."""
         import hashlib
         import numpy as np
         digest, status = b.download_content_hash()
         hx = digest.tobytes().hex()     # in bulk (as _detections: no per-file numpy work)
         hashes = [hx[i:i + 40] for i in range(0, len(hx), 40)]
         flagged = np.nonzero(status)[0].tolist()
+        self.host_hashed = len(flagged)
         if flagged:
             # contiguous slices, one per thread: few hand-overs of the GIL between the native calls
             k = max(1, min(self.nthreads, len(flagged) // 8))

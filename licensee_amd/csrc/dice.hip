@@ -306,6 +306,7 @@ static int transpose_to(dice_batch* b, const E* d_src, int64_t rows, int64_t col
 
 // The per-file scalars and, for the tile-layout kernels, the repack (the rows are in b->d_rows).
 // wf == NULL: |W_F| is already on the device (dice_batch_upload_text) and b->n_long is set.
+// len == NULL: the lengths are already on the device (dice_batch_upload_text_utf8 counted them).
 int dice::upload_tail(dice_batch* b, int64_t n, const uint32_t* wf, const int32_t* len, const uint8_t* cc,
                       hipStream_t s) {
     dice_ctx* c = b->ctx;
@@ -313,7 +314,7 @@ int dice::upload_tail(dice_batch* b, int64_t n, const uint32_t* wf, const int32_
     const int64_t npad = n_tiles * kWave;
     b->fmask_device = wf == nullptr;
     if (wf) HIP_TRY(hipMemcpyAsync(b->d_wf, wf, (size_t)n * 4, hipMemcpyHostToDevice, s));
-    HIP_TRY(hipMemcpyAsync(b->d_len, len, (size_t)n * 4, hipMemcpyHostToDevice, s));
+    if (len) HIP_TRY(hipMemcpyAsync(b->d_len, len, (size_t)n * 4, hipMemcpyHostToDevice, s));
     HIP_TRY(hipMemcpyAsync(b->d_cc, cc, (size_t)n, hipMemcpyHostToDevice, s));
     if (npad > n) {
         HIP_TRY(hipMemsetAsync(b->d_wf + n, 0, (size_t)(npad - n) * 4, s));
@@ -588,6 +589,7 @@ int dice_batch_upload(dice_batch* b, const dice_files* f, void* stream) {
     b->n_long = 0;
     b->fmask_device = false;
     b->text_state = 0;
+    b->text_utf8 = false;
     if (n == 0) return DICE_OK;
     HIP_TRY(hipMemcpyAsync(b->d_rows, f->bits, (size_t)n * c->w64 * 8, hipMemcpyHostToDevice, s));
     return dice::upload_tail(b, n, f->wordset_size, f->length, f->cc_false_positive, s);
@@ -604,6 +606,7 @@ int dice::upload_rows_resident(dice_batch* b, const dice_files* f, hipStream_t s
     b->n_long = 0;
     b->fmask_device = false;
     b->text_state = 0;
+    b->text_utf8 = false;
     if (b->n == 0) return DICE_OK;
     return upload_tail(b, b->n, f->wordset_size, f->length, f->cc_false_positive, s);
 }
@@ -630,6 +633,7 @@ int dice_batch_upload_ids(dice_batch* b, int64_t n, const int64_t* offsets, cons
     b->n_long = 0;
     b->fmask_device = false;
     b->text_state = 0;
+    b->text_utf8 = false;
     if (n == 0) return DICE_OK;
     const size_t need = (size_t)std::max<int64_t>(offsets[n], 1) * (size_t)id_bytes;
     if (need > b->ids_bytes) {

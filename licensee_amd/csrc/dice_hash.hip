@@ -4,10 +4,12 @@
 //   def content_hash; @content_hash ||= DIGEST.hexdigest content_normalized; end   (DIGEST = Digest::SHA1)
 // one of ProjectFile's HASH_METHODS (project_file.rb:17,97) and a field of `licensee detect`.
 //
-// The texts are those dice_batch_upload_text left in HBM (dice_words.hip: one byte per character,
-// every non-ASCII character as 0x80, 16-byte aligned offsets, 64 bytes of slack past the texts).
-// For an ASCII text these bytes are the UTF-8 of content_normalized, so their SHA-1 is content_hash;
-// a text with a byte >= 0x80 is flagged (status 1) and its digest is that of the resident bytes.
+// The texts are those an upload left in HBM (dice_words.hip: 16-byte aligned offsets, 64 bytes of
+// slack past the texts). After dice_batch_upload_text_utf8 they are the UTF-8 of content_normalized,
+// so their SHA-1 is content_hash and no file is flagged. After dice_batch_upload_text they hold one
+// byte per character, every non-ASCII character as 0x80: an ASCII text's digest is content_hash, a
+// text with a byte >= 0x80 is flagged (status 1) and its digest is that of the resident bytes. The
+// flag is (OR of the file's bytes) & flag_mask: 0x80808080 for the one-byte form, 0 for UTF-8.
 //
 // SHA-1 is one serial chain per message, so the parallelism is across files: one lane per file,
 // persistent. Every loop iteration each live lane runs one 64-byte block; a lane that finishes its
@@ -56,7 +58,7 @@ __global__ __launch_bounds__(kWave) void dice_sha1_kernel(const uint8_t* __restr
                                                           const int64_t* __restrict__ toff,
                                                           const int32_t* __restrict__ tlen, int64_t n,
                                                           uint32_t* __restrict__ next, uint32_t* __restrict__ digest,
-                                                          uint8_t* __restrict__ status) {
+                                                          uint8_t* __restrict__ status, uint32_t flag_mask) {
     int64_t f = atomicAdd(next, 1u);
     if (f >= n) return;
     const uint4* p = reinterpret_cast<const uint4*>(text + toff[f]);
@@ -135,7 +137,7 @@ __global__ __launch_bounds__(kWave) void dice_sha1_kernel(const uint8_t* __restr
             o[2] = __builtin_bswap32(h2);
             o[3] = __builtin_bswap32(h3);
             o[4] = __builtin_bswap32(h4);
-            status[f] = (seen & 0x80808080u) ? 1 : 0;
+            status[f] = (seen & flag_mask) ? 1 : 0;
             f = atomicAdd(next, 1u);
             if (f >= n) break;
             p = reinterpret_cast<const uint4*>(text + toff[f]);
@@ -172,7 +174,8 @@ extern "C" {
 int dice_batch_content_hash(dice_batch* b, void* stream) {
     if (!b) return fail(DICE_E_ARG, "NULL batch");
     dice_ctx* c = b->ctx;
-    if (!b->text_state) return fail(DICE_E_STATE, "the batch's last upload was not dice_batch_upload_text");
+    if (!b->text_state)
+        return fail(DICE_E_STATE, "the batch's last upload was not dice_batch_upload_text or dice_batch_upload_text_utf8");
     const int64_t n = b->n;
     if (n == 0) {
         b->text_state = 2;
@@ -190,7 +193,8 @@ int dice_batch_content_hash(dice_batch* b, void* stream) {
     // taken from the counter
     const int64_t waves = std::min<int64_t>((n + dice::kWave - 1) / dice::kWave, (int64_t)c->n_cu * 16);
     hipLaunchKernelGGL(dice::dice_sha1_kernel, dim3((unsigned)waves), dim3(dice::kWave), 0, s, (const uint8_t*)b->d_text,
-                       (const int64_t*)b->d_toff, (const int32_t*)b->d_tlen, n, b->d_hcnt, (uint32_t*)b->d_hdig, b->d_hstat);
+                       (const int64_t*)b->d_toff, (const int32_t*)b->d_tlen, n, b->d_hcnt, (uint32_t*)b->d_hdig, b->d_hstat,
+                       b->text_utf8 ? 0u : 0x80808080u);
     if (hipGetLastError() != hipSuccess) return fail(DICE_E_DEVICE, "dice_sha1_kernel launch failed");
     b->text_state = 2;
     return DICE_OK;

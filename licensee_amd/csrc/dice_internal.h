@@ -155,8 +155,8 @@ int download_topk_to(dice_batch* b, int32_t* tki, double* tks, hipStream_t s, hi
 void exact_free(dice_ctx* c);
 // the device wordset tables (dice_words.hip)
 void words_free(dice_ctx* c);
-// dice_batch_upload's tail: per-file scalars (wf == NULL: already on the device, b->n_long set),
-// padding, and the tile repack (dice.hip)
+// dice_batch_upload's tail: per-file scalars (wf == NULL: already on the device, b->n_long set;
+// len == NULL: already on the device), padding, and the tile repack (dice.hip)
 int upload_tail(dice_batch* b, int64_t n, const uint32_t* wf, const int32_t* len, const uint8_t* cc, hipStream_t s);
 // the tile-layout kernels' repack of b->d_rows (no-op for the postings kernels)
 int repack(dice_batch* b, hipStream_t s);
@@ -214,8 +214,11 @@ struct dice_batch {
     // dice_batch_content_hash (dice_hash.hip): 0 = the last upload left no text resident, 1 = the
     // texts of dice_batch_upload_text are resident, 2 = and their digests are computed (or queued)
     int32_t text_state = 0;
+    // the resident texts are UTF-8 (dice_batch_upload_text_utf8; every other upload clears it): their
+    // bytes are content_normalized's, so dice_batch_content_hash flags no file
+    bool text_utf8 = false;
     uint8_t* d_hdig = nullptr;      // [capacity][20] SHA-1 digests
-    uint8_t* d_hstat = nullptr;     // [capacity] 1 = the text holds a byte >= 0x80
+    uint8_t* d_hstat = nullptr;     // [capacity] 1 = one-byte-per-character text with a byte >= 0x80
     uint32_t* d_hcnt = nullptr;     // the kernel's next-file counter
     // small-call batch: d_wf/d_len/d_cc/d_rows carved from d_in, results from d_out
     void *d_in = nullptr, *d_out = nullptr;

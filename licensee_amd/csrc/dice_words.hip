@@ -6,8 +6,9 @@
 // with WORDSET_REGEX = /(?:[\w\/-](?:'s|(?<=s)')?)+/ (ASCII \w) over content_normalized, and the
 // interning of those words into the corpus vocabulary's bitset (what dice_files.bits holds:
 // licensee_amd/corpus.py) with |W_F| counting every distinct word, vocabulary or not
-// (content_helper.rb:128-133 divides by wordset.size). The texts arrive normalized
-// (licensee_host.h lh_normalize_files: one byte per character, non-ASCII characters as 0x80).
+// (content_helper.rb:128-133 divides by wordset.size). The texts arrive normalized, either one byte
+// per character with non-ASCII characters as 0x80 (licensee_host.h lh_normalize_files) or as UTF-8
+// (lh_normalize_files_utf8): the scan is the same, since every byte >= 0x80 only separates tokens.
 //
 // One wave per file, persistent over the batch. The file streams through a per-wave LDS window of
 // two 1 KiB chunks (one 16-byte load per lane, the chunk after next in flight while this one is
@@ -646,6 +647,62 @@ __global__ __launch_bounds__(kWordsWaves * kWave) __attribute__((amdgpu_waves_pe
     }
 }
 
+
+// content_normalized.length of every resident UTF-8 text (dice_batch_upload_text_utf8 without the
+// caller's lengths): the characters of file f are the bytes of [off, off + tlen) that are not
+// UTF-8 continuation bytes, (b & 0xC0) != 0x80. One wave per file: wave w takes files
+// [w * per_wave, (w + 1) * per_wave), and per_wave is 1 until the batch has more files than the
+// device holds waves (8 per SIMD). (Taking the files from a counter, as the scan does, cost more
+// than the counting: the kernel moves ~9 KB per file, and every wave's atomicAdd on the one counter
+// waits for the others' -- 89 us against 7 us of loads for 4,000 texts, profiles/content_hash_utf8.txt.
+// A file here is microseconds of work, so uneven sizes leave no tail worth balancing.)
+// A lane reads aligned 16-byte groups, kCharsLoads
+// of them requested before the first is counted (a wave covers 4 KiB per round); a group is loaded
+// only when it starts inside the file, so no load leaves the allocation even when the last file
+// ends exactly at text_bytes; bytes at or past tlen (another file's padding, slack) are masked,
+// never trusted. Per dword the continuation bytes are bit 7 set and bit 6 clear (SWAR: x & ~(x << 1)
+// on the bit-7 plane -- the shift moves each byte's bit 6 to its own bit 7), counted by one popcount.
+constexpr int kCharsWaves = 4;   // waves (files in flight) per workgroup
+constexpr int kCharsLoads = 4;   // 16-byte groups a lane has in flight
+
+__global__ __launch_bounds__(kCharsWaves * kWave) void dice_text_chars_kernel(
+    const uint8_t* __restrict__ text, const int64_t* __restrict__ off, const int32_t* __restrict__ tlen, int64_t n,
+    int32_t per_wave, int32_t* __restrict__ length) {
+    const int lane = threadIdx.x & (kWave - 1);
+    const int64_t w = (int64_t)blockIdx.x * kCharsWaves + (int64_t)rfl(threadIdx.x >> 6);
+    const int64_t f_end = min((w + 1) * per_wave, n);
+    for (int64_t f = w * per_wave; f < f_end; ++f) {
+        const int64_t fo = (int64_t)(((uint64_t)rfl((uint32_t)((uint64_t)off[f] >> 32)) << 32) | rfl((uint32_t)off[f]));
+        const uint32_t nb = rfl((uint32_t)tlen[f]);
+        const uint4* p = reinterpret_cast<const uint4*>(text + fo);
+        uint32_t chars = 0;
+        for (uint32_t g0 = 0; g0 * 16u < nb; g0 += kCharsLoads * kWave) {   // (nb < 2^31: no wrap)
+            uint4 q[kCharsLoads];
+#pragma unroll
+            for (int j = 0; j < kCharsLoads; ++j) {
+                const uint32_t g = g0 + (uint32_t)(j * kWave + lane);
+                q[j] = make_uint4(0u, 0u, 0u, 0u);
+                if (g * 16u < nb) q[j] = p[g];
+            }
+#pragma unroll
+            for (int j = 0; j < kCharsLoads; ++j) {
+                const uint32_t at = (g0 + (uint32_t)(j * kWave + lane)) * 16u;   // the group's first byte
+                const uint32_t x[4] = {q[j].x, q[j].y, q[j].z, q[j].w};
+#pragma unroll
+                for (int k = 0; k < 4; ++k) {
+                    // bit 7 of the dword's bytes inside the file
+                    const uint32_t a = at + 4u * k;
+                    const uint32_t in = a >= nb ? 0u : nb - a >= 4u ? 0x80808080u : 0x80808080u & ((1u << (8u * (nb - a))) - 1u);
+                    const uint32_t cont = x[k] & ~(x[k] << 1);
+                    chars += (uint32_t)__builtin_popcount(~cont & in);
+                }
+            }
+        }
+        const uint32_t total = wave_sum(chars);
+        if (lane == 0) length[f] = (int32_t)total;
+    }
+}
+
 }  // namespace dice
 
 // ---- host side ---------------------------------------------------------------------------
@@ -792,14 +849,18 @@ int dice_vocab_setup(dice_ctx* c, int32_t n_words, const char* const* words, int
     return DICE_OK;
 }
 
-int dice_batch_upload_text(dice_batch* b, int64_t n, const uint8_t* text, int64_t text_bytes, const int64_t* offsets,
-                           const int32_t* text_len, const int32_t* length, const uint8_t* cc, uint8_t* status,
-                           int64_t* n_overflow, void* stream) {
+// dice_batch_upload_text and dice_batch_upload_text_utf8: the texts to the device, the wordset scan,
+// the per-file scalars. utf8: the texts are UTF-8 (text_len in bytes), and length == NULL has the
+// device count each file's characters (dice_text_chars_kernel) instead of copying the caller's.
+static int upload_text(dice_batch* b, bool utf8, int64_t n, const uint8_t* text, int64_t text_bytes,
+                       const int64_t* offsets, const int32_t* text_len, const int32_t* length, const uint8_t* cc,
+                       uint8_t* status, int64_t* n_overflow, void* stream) {
     if (!b) return fail(DICE_E_ARG, "NULL batch");
     dice_ctx* c = b->ctx;
     if (!c->words_ready) return fail(DICE_E_STATE, "dice_vocab_setup was not called");
     if (n < 0 || n > b->capacity) return fail(DICE_E_ARG, "n_files exceeds batch capacity");
-    if (n > 0 && (!text || !offsets || !text_len || !length || !cc || !status)) return fail(DICE_E_ARG, "NULL file arrays");
+    if (n > 0 && (!text || !offsets || !text_len || (!length && !utf8) || !cc || !status))
+        return fail(DICE_E_ARG, "NULL file arrays");
     if (text_bytes < 0) return fail(DICE_E_ARG, "negative text_bytes");
     for (int64_t i = 0; i < n; ++i) {
         if (offsets[i] < 0 || (offsets[i] & 15) || text_len[i] < 0 || offsets[i] + text_len[i] > text_bytes)
@@ -823,12 +884,21 @@ int dice_batch_upload_text(dice_batch* b, int64_t n, const uint8_t* text, int64_
     b->n = n;
     b->n_long = 0;
     b->text_state = n == 0;   // (dice_batch_content_hash: the texts are resident once this call succeeds)
+    b->text_utf8 = utf8;
     if (n_overflow) *n_overflow = 0;
     if (n == 0) return DICE_OK;
     if (hipMemcpyAsync(b->d_text, text, (size_t)text_bytes, hipMemcpyHostToDevice, s) != hipSuccess ||
         hipMemcpyAsync(b->d_toff, offsets, (size_t)n * 8, hipMemcpyHostToDevice, s) != hipSuccess ||
         hipMemcpyAsync(b->d_tlen, text_len, (size_t)n * 4, hipMemcpyHostToDevice, s) != hipSuccess ||
         hipMemsetAsync(b->d_wcnt, 0, 16, s) != hipSuccess)   // (overflow, long, next file)
+        return fail(DICE_E_DEVICE, "text upload failed");
+    // The scan reads whole 16-byte groups and takes one that reaches past the text as zeros: a last
+    // file ending at a text_bytes that is no multiple of 16 would lose its tail. The bytes up to the
+    // next multiple (inside the 64 bytes of slack) are zeroed and the scan is given that size;
+    // offsets are 16-byte aligned, so every group of a file then lies inside it.
+    const int64_t scan_bytes = (text_bytes + 15) & ~(int64_t)15;
+    if (scan_bytes > text_bytes &&
+        hipMemsetAsync(b->d_text + text_bytes, 0, (size_t)(scan_bytes - text_bytes), s) != hipSuccess)
         return fail(DICE_E_DEVICE, "text upload failed");
     dice::VocabDev v;
     v.slots = (const uint32_t*)c->d_wslots;
@@ -843,10 +913,21 @@ int dice_batch_upload_text(dice_batch* b, int64_t n, const uint8_t* text, int64_
     const size_t lds = dice::words_lds_per_wave(c->w64) * dice::kWordsWaves;
     const int64_t groups = std::min<int64_t>((n + dice::kWordsWaves - 1) / dice::kWordsWaves, (int64_t)c->n_cu * 4);
     hipLaunchKernelGGL(dice::dice_words_kernel, dim3((unsigned)groups), dim3(dice::kWordsWaves * dice::kWave), lds, s,
-                       (const uint8_t*)b->d_text, text_bytes, (const int64_t*)b->d_toff, (const int32_t*)b->d_tlen, n, v,
+                       (const uint8_t*)b->d_text, scan_bytes, (const int64_t*)b->d_toff, (const int32_t*)b->d_tlen, n, v,
                        c->w64, b->d_rows, b->d_wf, b->d_fmask, b->d_wstat, b->d_wcnt,
                        c->kind == 3 && c->prune ? c->prune_max_lf : 0xFFFFFFFFu);
     if (hipGetLastError() != hipSuccess) return fail(DICE_E_DEVICE, "dice_words_kernel launch failed");
+    if (!length) {   // (the same stream: the status download below is still the call's one synchronization)
+        // one file per wave while the device holds that many waves (8 per SIMD), else equal shares
+        const int64_t wmax = (int64_t)c->n_cu * 32;
+        const int64_t per_wave = (n + wmax - 1) / wmax;
+        const int64_t waves = (n + per_wave - 1) / per_wave;
+        const int64_t cg = (waves + dice::kCharsWaves - 1) / dice::kCharsWaves;
+        hipLaunchKernelGGL(dice::dice_text_chars_kernel, dim3((unsigned)cg), dim3(dice::kCharsWaves * dice::kWave), 0, s,
+                           (const uint8_t*)b->d_text, (const int64_t*)b->d_toff, (const int32_t*)b->d_tlen, n,
+                           (int32_t)per_wave, b->d_len);
+        if (hipGetLastError() != hipSuccess) return fail(DICE_E_DEVICE, "dice_text_chars_kernel launch failed");
+    }
     uint32_t cnt[2] = {0, 0};
     if (hipMemcpyAsync(status, b->d_wstat, (size_t)n, hipMemcpyDeviceToHost, s) != hipSuccess ||
         hipMemcpyAsync(cnt, b->d_wcnt, 8, hipMemcpyDeviceToHost, s) != hipSuccess ||
@@ -857,6 +938,28 @@ int dice_batch_upload_text(dice_batch* b, int64_t n, const uint8_t* text, int64_
     rc = dice::upload_tail(b, n, nullptr, length, cc, s);
     b->text_state = rc == DICE_OK;
     return rc;
+}
+
+int dice_batch_upload_text(dice_batch* b, int64_t n, const uint8_t* text, int64_t text_bytes, const int64_t* offsets,
+                           const int32_t* text_len, const int32_t* length, const uint8_t* cc, uint8_t* status,
+                           int64_t* n_overflow, void* stream) {
+    return upload_text(b, false, n, text, text_bytes, offsets, text_len, length, cc, status, n_overflow, stream);
+}
+
+int dice_batch_upload_text_utf8(dice_batch* b, int64_t n, const uint8_t* text, int64_t text_bytes,
+                                const int64_t* offsets, const int32_t* text_len, const int32_t* length,
+                                const uint8_t* cc, uint8_t* status, int64_t* n_overflow, void* stream) {
+    return upload_text(b, true, n, text, text_bytes, offsets, text_len, length, cc, status, n_overflow, stream);
+}
+
+int dice_batch_download_length(dice_batch* b, int32_t* length, void* stream) {
+    if (!b) return fail(DICE_E_ARG, "NULL batch");
+    dice_ctx* c = b->ctx;
+    dice::WGuard g(c->device);
+    hipStream_t s = stream ? (hipStream_t)stream : c->stream;
+    if (b->n && length && hipMemcpyAsync(length, b->d_len, (size_t)b->n * 4, hipMemcpyDeviceToHost, s) != hipSuccess)
+        return fail(DICE_E_DEVICE, "length download failed");
+    return hipStreamSynchronize(s) == hipSuccess ? DICE_OK : fail(DICE_E_DEVICE, "hipStreamSynchronize failed");
 }
 
 int dice_batch_set_rows(dice_batch* b, int64_t k, const int64_t* index, const uint64_t* bits, const uint32_t* wordset_size,

@@ -1289,14 +1289,17 @@ int64_t lh_normalize(lh_ctx* ctx, const char* data, int64_t len, const char* fil
     return (int64_t)u.size();
 }
 
-// Batched content_normalized for the device wordset scan (liblicensee_dice dice_batch_upload_text):
-// each file's normalized text as bytes, a non-ASCII character as the one byte 0x80 (the wordset's
-// [\w/-] is ASCII, content_helper.rb:109, so any such byte only separates tokens), placed at a
-// 16-byte aligned offset of `out` in completion order (a bump allocator over `cap` bytes).
-int64_t lh_normalize_files(lh_ctx* ctx, int64_t n, const char* const* data, const int64_t* lens,
-                           const char* const* filenames, int32_t nthreads, char* out, int64_t cap, int64_t* off,
-                           int32_t* tlen, int32_t* length, uint8_t* cc, uint8_t* copyright, uint8_t* status) {
-    const Ctx* c = reinterpret_cast<const Ctx*>(ctx);
+}  // extern "C"
+
+namespace {
+
+// Batched content_normalized for the device wordset scan: each file's normalized text placed at a
+// 16-byte aligned offset of `out` in completion order (a bump allocator over `cap` bytes). The two
+// entry points differ only in how a non-ASCII text is written out: one byte per character (every
+// non-ASCII character as 0x80), or its UTF-8; an ASCII text is one memcpy in both.
+int64_t normalize_files(const Ctx* c, bool utf8, int64_t n, const char* const* data, const int64_t* lens,
+                        const char* const* filenames, int32_t nthreads, char* out, int64_t cap, int64_t* off,
+                        int32_t* tlen, int32_t* length, uint8_t* cc, uint8_t* copyright, uint8_t* status) {
     if (n < 0 || cap < 0 || (n > 0 && (!data || !lens || !out || !off || !tlen || !length || !cc || !copyright || !status)))
         return -1;
     if (nthreads < 1) nthreads = 1;
@@ -1312,8 +1315,11 @@ int64_t lh_normalize_files(lh_ctx* ctx, int64_t n, const char* const* data, cons
                 tlen[f] = 0;
                 status[f] = (uint8_t)o.status;
                 if (o.status) continue;
-                const size_t sz = o.ascii ? o.normalized8.size() : o.normalized.size();
-                length[f] = (int32_t)sz;   // characters (one byte per character in `out`)
+                const size_t chars = o.ascii ? o.normalized8.size() : o.normalized.size();
+                std::string u8;   // a non-ASCII text's UTF-8 (the bytes lh_normalize writes)
+                if (utf8 && !o.ascii) u8 = rx::to_utf8(o.normalized);
+                const size_t sz = utf8 && !o.ascii ? u8.size() : chars;   // bytes in `out`
+                length[f] = (int32_t)chars;
                 cc[f] = o.cc;
                 copyright[f] = o.copyright;
                 const int64_t need = (int64_t)((sz + 15) & ~(size_t)15);
@@ -1327,6 +1333,8 @@ int64_t lh_normalize_files(lh_ctx* ctx, int64_t n, const char* const* data, cons
                 char* dst = out + at;
                 if (o.ascii) {
                     memcpy(dst, o.normalized8.data(), sz);
+                } else if (utf8) {
+                    memcpy(dst, u8.data(), sz);
                 } else {
                     for (size_t k = 0; k < sz; ++k) {
                         const char32_t ch = o.normalized[k];
@@ -1343,6 +1351,30 @@ int64_t lh_normalize_files(lh_ctx* ctx, int64_t n, const char* const* data, cons
     };
     run_workers(nthreads, work);
     return used.load();
+}
+
+}  // namespace
+
+extern "C" {
+
+// liblicensee_dice dice_batch_upload_text: one byte per character, a non-ASCII character as the one
+// byte 0x80 (the wordset's [\w/-] is ASCII, content_helper.rb:109, so any such byte only separates
+// tokens); tlen[i] == length[i].
+int64_t lh_normalize_files(lh_ctx* ctx, int64_t n, const char* const* data, const int64_t* lens,
+                           const char* const* filenames, int32_t nthreads, char* out, int64_t cap, int64_t* off,
+                           int32_t* tlen, int32_t* length, uint8_t* cc, uint8_t* copyright, uint8_t* status) {
+    return normalize_files(reinterpret_cast<const Ctx*>(ctx), false, n, data, lens, filenames, nthreads, out, cap, off,
+                           tlen, length, cc, copyright, status);
+}
+
+// liblicensee_dice dice_batch_upload_text_utf8: the UTF-8 of content_normalized, the bytes
+// lh_normalize writes (so their SHA-1 is content_hash, content_helper.rb:136-138); tlen[i] in bytes,
+// length[i] in characters.
+int64_t lh_normalize_files_utf8(lh_ctx* ctx, int64_t n, const char* const* data, const int64_t* lens,
+                                const char* const* filenames, int32_t nthreads, char* out, int64_t cap, int64_t* off,
+                                int32_t* tlen, int32_t* length, uint8_t* cc, uint8_t* copyright, uint8_t* status) {
+    return normalize_files(reinterpret_cast<const Ctx*>(ctx), true, n, data, lens, filenames, nthreads, out, cap, off,
+                           tlen, length, cc, copyright, status);
 }
 
 // Batched LicenseFile preparation: decode, normalize, wordset scan, intern to the vocabulary

@@ -44,6 +44,8 @@ def _load():
         l.lh_template_field_masks.argtypes = [vp, vp]
         l.lh_normalize_files.restype = i64
         l.lh_normalize_files.argtypes = [vp, i64, cpp, vp, cpp, i32, vp, i64, vp, vp, vp, vp, vp, vp]
+        l.lh_normalize_files_utf8.restype = i64
+        l.lh_normalize_files_utf8.argtypes = l.lh_normalize_files.argtypes
         l.lh_set_unicode.restype = ctypes.c_int
         l.lh_set_unicode.argtypes = [vp, i32, vp, vp, i32, vp, vp]
         _lib = l
@@ -269,13 +271,16 @@ class HostPrep:
         return FileBatch(bits, wf, ln, cc), cr.astype(bool), ex, fell
 
     def normalize_files(self, contents: Sequence[Union[str, bytes]], filenames: Optional[Sequence[str]] = None,
-                        nthreads: int = 8, out=None):
+                        nthreads: int = 8, out=None, utf8: bool = False):
         """Batched content_normalized for the device wordset scan (``lh_normalize_files``;
         ``DeviceBatch.upload_text``). Returns (text uint8 [bytes], offsets [n] int64 (16-byte
         aligned), text_len [n] int32, length [n] int32, cc [n] uint8, copyright [n] bool, fell [n]
         bool): file i's normalized text at ``text[offsets[i]:offsets[i] + text_len[i]]``, one byte
         per character (non-ASCII characters as 0x80: the wordset's ``[\\w/-]`` is ASCII). Files the
         native path does not cover (``fell``) are normalized by the Python path and appended.
+        ``utf8=True`` (``lh_normalize_files_utf8``; ``upload_text(..., utf8=True)``): every text,
+        the appended ones too, is the UTF-8 of content_normalized, ``text_len`` in bytes and
+        ``length`` in characters.
         ``out``: a callable ``out(nbytes) -> uint8 array`` giving the buffer to write into (e.g. a
         page-locked one, ``_native.PinnedBuffer``); default a new numpy array."""
         lib = _load()
@@ -295,9 +300,9 @@ class HostPrep:
         cc = np.zeros(n, np.uint8)
         cr = np.zeros(n, np.uint8)
         st = np.zeros(n, np.uint8)
-        used = lib.lh_normalize_files(self._c, n, data, lens.ctypes.data, fns, nthreads, buf.ctypes.data, cap,
-                                      off.ctypes.data, tl.ctypes.data, ln.ctypes.data, cc.ctypes.data,
-                                      cr.ctypes.data, st.ctypes.data)
+        fn = lib.lh_normalize_files_utf8 if utf8 else lib.lh_normalize_files
+        used = fn(self._c, n, data, lens.ctypes.data, fns, nthreads, buf.ctypes.data, cap, off.ctypes.data,
+                  tl.ctypes.data, ln.ctypes.data, cc.ctypes.data, cr.ctypes.data, st.ctypes.data)
         if used < 0:
             raise RuntimeError('lh_normalize_files failed')
         # the rest by Python (no room left: rare expansions; outside the native envelope), appended
@@ -317,7 +322,10 @@ class HostPrep:
             parts = []
             at = int(used)
             for i, txt, flags in extra:
-                b = bytes(c if c < 0x80 else 0x80 for c in (ord(ch) for ch in txt)) if not txt.isascii() else txt.encode()
+                if utf8 or txt.isascii():
+                    b = txt.encode('utf-8')
+                else:
+                    b = bytes(c if c < 0x80 else 0x80 for c in (ord(ch) for ch in txt))
                 off[i] = at
                 tl[i] = len(b)
                 ln[i] = len(txt)
