@@ -24,6 +24,9 @@
  *                                   devices of one node (the dice.rb:34-41 loop is per file)
  *   dice_batch_*                    device-resident batch variants of the two calls above
  *                                   (inputs as bitsets or as word-id lists)
+ *   dice_batch_projects             Project#license / #licenses / #matched_file over the license files of many
+ *                                   projects at once                 lib/licensee/projects/project.rb:24-47,102-106,137-155
+ *                                   on LicenseFile#license           lib/licensee/project_files/license_file.rb:84-98
  *   dice_last_error                 replaces the Ruby exceptions of the path (license.rb:258,
  *                                   content_helper.rb:230,310) with status codes + message
  *
@@ -327,6 +330,55 @@ int dice_batch_content_hash(dice_batch *batch, void *stream);
  * hashes that file's UTF-8 itself.
  * NULL outputs are skipped; DICE_E_STATE if no hash was computed since the last upload. */
 int dice_batch_download_content_hash(dice_batch *batch, uint8_t *digest, uint8_t *status, void *stream);
+
+/* ---- Project#license on the device ------------------------------------------------------
+ * Project#license, #licenses and #matched_file (projects/project.rb:24-47) for groups of the
+ * resident files, with detect_readme and detect_packages false (the reference's default): project
+ * p owns the files [offsets[p], offsets[p + 1]) of the batch, its license files in license_files
+ * order before prioritize_lgpl (project.rb:54-66,111-117: name score descending, files that score
+ * 0 already dropped by the caller). offsets is non-decreasing with offsets[0] == 0 and
+ * offsets[n_projects] == the batch's file count; empty projects are legal.
+ *   file_flags[i]      bit 0: the Copyright matcher matched the file (copyright.rb; the host's result)
+ *                      bit 1: the name is a copyright? name          (project_file.rb:90-95)
+ *                      bit 2: lesser_gpl_score(name) == 1            (license_file.rb:105-107)
+ *   template_flags[t]  bit 0: gpl?, bit 1: lgpl?                     (license.rb:200-206)
+ * License ids: 0 .. T-1 the templates, T = License 'other', T + 1 = 'no-license', -1 = nil.
+ * LicenseFile#license per file (license_file.rb:92-98 over [Copyright, Exact, Dice]), from the
+ * batch's resident Exact and match results (nothing is uploaded again):
+ *   L(i) = flags & 1 ? T + 1 : (use_exact && exact[i] >= 0) ? exact[i] : best[i] >= 0 ? best[i] : T
+ * Per project:
+ *   license       Project#license (project.rb:24-32), -1 for nil: no file, or only copyright? files
+ *   matched_file  the batch index of Project#matched_file (:40-42), or -1
+ *   n_licenses    Project#licenses.count (:35-37): the distinct L(i), copyright? files included
+ *   licenses      [n_projects][k_licenses]: the first k_licenses entries of Project#licenses -- file
+ *                 order after prioritize_lgpl (:137-145), first occurrences -- padded with -1;
+ *                 k_licenses in [0, DICE_PROJECT_K_MAX]
+ * The order of files of equal name score is parity-unpinned in the reference (find_files sorts with
+ * an unstable sort): license and matched_file do not depend on it, licenses lists what the caller's
+ * order gives.
+ * State: DICE_E_STATE unless dice_batch_match or dice_batch_match_confidence has run since the
+ * batch's last upload, and, with use_exact != 0, unless dice_batch_exact has; the download calls are
+ * DICE_E_STATE unless dice_batch_projects has run since the last upload. A NULL batch, NULL or
+ * inconsistent offsets, NULL flags, k_licenses out of range and a negative n_projects are DICE_E_ARG.
+ * dice_batch_projects is asynchronous on `stream` (no host synchronization inside unless its buffers
+ * grow): offsets and flags are copied from host memory on that stream, so they must stay valid until
+ * it has run. Its buffers are allocated on the first call and grown with n_projects.
+ * dice_batch_download_projects synchronizes `stream`; any output may be NULL. */
+#define DICE_PROJECT_K_MAX 8
+int dice_batch_projects(dice_batch *batch, int64_t n_projects, const int64_t *offsets,
+                        const uint8_t *file_flags, const uint8_t *template_flags,
+                        int32_t use_exact, int32_t k_licenses, void *stream);
+int dice_batch_download_projects(dice_batch *batch, int32_t *license, int32_t *matched_file,
+                                 int32_t *n_licenses, int32_t *licenses, void *stream);
+/* What a caller reports about Project#matched_file (project_file.rb:69-76), gathered by the resolve
+ * so that only one entry per project is downloaded: matcher[p] = 0 Copyright, 1 Exact, 2 Dice, -1 no
+ * matcher (the file's license is 'other') or no matched file; confidence[p] = 100 for Copyright and
+ * Exact, Dice#confidence for Dice, else 0; digest [n_projects][20] = the matched file's content_hash
+ * (zeros without one) when dice_batch_content_hash ran before the resolve, DICE_E_STATE for a
+ * non-NULL digest otherwise. Same state rule and synchronization as dice_batch_download_projects;
+ * NULL outputs are skipped. */
+int dice_batch_download_project_match(dice_batch *batch, int32_t *matcher, double *confidence,
+                                      uint8_t *digest, void *stream);
 
 /* Build step (no device needed): generate + compile the corpus-specialized sparse program
  * with hiprtc for gfx950 and store it in the code-object cache; writes the cache path. */

@@ -17,6 +17,7 @@ LIB_PATH = os.path.join(LIB_DIR, 'liblicensee_dice.so')
 
 DICE_OK = 0
 DICE_TOPK_MAX = 16
+DICE_PROJECT_K_MAX = 8
 
 EXPORTED_SYMBOLS = (
     'dice_words64', 'dice_create', 'dice_destroy', 'dice_ctx_info', 'dice_match',
@@ -34,6 +35,7 @@ EXPORTED_SYMBOLS = (
     'dice_program_mfma_rows', 'dice_batch_content_hash', 'dice_batch_download_content_hash',
     'dice_topk', 'dice_topk_sharded', 'dice_batch_topk', 'dice_batch_download_topk', 'dice_batch_matrix_bytes',
     'dice_batch_upload_text_utf8', 'dice_batch_download_length',
+    'dice_batch_projects', 'dice_batch_download_projects', 'dice_batch_download_project_match',
 )
 DICE_GATHER_HOST = 0
 DICE_GATHER_DEVICE = 1
@@ -220,6 +222,9 @@ def load_library(path: str = LIB_PATH) -> ctypes.CDLL:
         'dice_batch_topk': (ctypes.c_int, [vp, i32, vp]),
         'dice_batch_download_topk': (ctypes.c_int, [vp, i32, vp, vp, vp]),
         'dice_batch_matrix_bytes': (i64, [vp]),
+        'dice_batch_projects': (ctypes.c_int, [vp, i64, vp, vp, vp, i32, i32, vp]),
+        'dice_batch_download_projects': (ctypes.c_int, [vp, vp, vp, vp, vp, vp]),
+        'dice_batch_download_project_match': (ctypes.c_int, [vp, vp, vp, vp, vp]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)
@@ -618,6 +623,41 @@ class DeviceBatch:
         status = np.empty(self.n, np.uint8)
         _check(load_library().dice_batch_download_content_hash(self._b, _ptr(digest), _ptr(status), stream or None))
         return digest, status
+
+    def projects(self, offsets, file_flags, template_flags, use_exact: bool = True, k: int = 4, stream: int = 0):
+        """``dice_batch_projects``: Project#license / #licenses / #matched_file (project.rb:24-47) of
+        the projects ``offsets`` ([P + 1] int64) cuts the resident files into, from the resident Exact
+        and match results (asynchronous). ``file_flags`` [n] uint8: bit 0 Copyright matched, bit 1 a
+        copyright? name, bit 2 COPYING.lesser; ``template_flags`` [T] uint8: bit 0 gpl?, bit 1 lgpl?."""
+        off = np.ascontiguousarray(offsets, dtype=np.int64)
+        ff = np.ascontiguousarray(file_flags, dtype=np.uint8)
+        tf = np.ascontiguousarray(template_flags, dtype=np.uint8)
+        if off.ndim != 1 or off.shape[0] < 1 or ff.shape != (self.n,) or tf.shape != (self.scorer.n_templates,):
+            raise ValueError('projects: offsets [P + 1], file_flags [n], template_flags [T]')
+        self._proj = (off, ff, tf)   # the H2D copies may still read them after the call returns
+        self.n_projects, self.k_licenses = off.shape[0] - 1, int(k)
+        _check(load_library().dice_batch_projects(self._b, self.n_projects, _ptr(off), _ptr(ff) if ff.size else None,
+                                                  _ptr(tf), int(bool(use_exact)), int(k), stream or None))
+
+    def download_projects(self, stream: int = 0):
+        """(license [P], matched_file [P], n_licenses [P], licenses [P, k]) int32 of the last
+        :meth:`projects`: template index, T = 'other', T + 1 = 'no-license', -1 = nil / padding."""
+        P, k = getattr(self, 'n_projects', 0), getattr(self, 'k_licenses', 0)
+        lic, mf, nl = (np.empty(P, np.int32) for _ in range(3))
+        lst = np.empty((P, k), np.int32)
+        _check(load_library().dice_batch_download_projects(self._b, _ptr(lic), _ptr(mf), _ptr(nl),
+                                                           _ptr(lst) if k else None, stream or None))
+        return lic, mf, nl, lst
+
+    def download_project_match(self, digest: bool = False, stream: int = 0):
+        """(matcher [P] int32: 0 copyright, 1 exact, 2 dice, -1 none; confidence [P] float64; digest
+        [P, 20] uint8 or None) of every project's matched file (``dice_batch_download_project_match``)."""
+        P = getattr(self, 'n_projects', 0)
+        mt = np.empty(P, np.int32)
+        cf = np.empty(P, np.float64)
+        dg = np.empty((P, 20), np.uint8) if digest else None
+        _check(load_library().dice_batch_download_project_match(self._b, _ptr(mt), _ptr(cf), _ptr(dg), stream or None))
+        return mt, cf, dg
 
     def deferred(self, stream: int = 0) -> int:
         """Files the bound-pruned kernel handed to the postings kernels in the last match."""

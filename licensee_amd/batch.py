@@ -17,6 +17,11 @@ The reference evaluates ``[Copyright, Exact, Dice].map(new).find(&:match)`` per 
 ``exact_on='host'`` keeps Exact in the host threads too, the round-2 split.)
 
 Results equal the per-file Python chain (tests/test_gpu_golden.py::test_batch_chain).
+
+``detect_projects`` answers for whole projects (Project#license, projects/project.rb:24-32): the
+license files of all projects go through the same single upload / Exact / match, the device reduces
+the resident per-file results to one record per project (dice_batch_projects), and only those
+records are downloaded and turned into objects (tests/test_gpu_projects.py).
 """
 from __future__ import annotations
 
@@ -33,6 +38,18 @@ class Detection:
     matcher: Optional[str]      # 'copyright' | 'exact' | 'dice' | None
     confidence: object          # 100 (copyright/exact), Float (dice), None (no matcher)
     content_hash: Optional[str] = None   # content_hash (SHA-1 hex), BatchDetector(content_hash=True) only
+
+
+@dataclass(slots=True)
+class ProjectDetection:
+    license: Optional[License]          # Project#license (project.rb:24-32); None for nil
+    matched_file: Optional[str]         # Project#matched_file's filename (project.rb:40-42), or None
+    matcher: Optional[str]              # the matched file's matcher: 'copyright' | 'exact' | 'dice' | None
+    confidence: object                  # its confidence: 100, Float (dice), None (no matcher or no matched file)
+    licenses: List[License]             # the first k_licenses entries of Project#licenses (project.rb:35-37)
+    n_licenses: int                     # Project#licenses.count, exact
+    n_files: int                        # Project#license_files.count
+    content_hash: Optional[str] = None  # the matched file's content_hash, BatchDetector(content_hash=True) only
 
 
 class BatchDetector:
@@ -73,6 +90,7 @@ class BatchDetector:
         self._turn = 0
         self._pool = None           # threads of the content-hash completion (content_hash=True, on demand)
         self.host_hashed = 0        # files of the last batch whose content_hash came from the host
+        self._name_info = {}        # detect_projects: filename -> (name score, name bits)
         if self.exact_on == 'device':
             self.engine.scorer.exact_setup(*exact_tables(self.engine.corpus, self.host))
         if self.wordset_on == 'device':
@@ -133,6 +151,118 @@ class BatchDetector:
                 fut = ex.submit(self._prep, *nxt) if nxt is not None else None
                 yield self._score(prepped, thr)
 
+    def detect_projects(self, projects: Sequence[Sequence[Tuple[str, Union[str, bytes]]]], threshold=None,
+                        k_licenses: int = 4) -> List[ProjectDetection]:
+        """Project#license, #matched_file and #licenses (projects/project.rb:24-47; detect_readme and
+        detect_packages false) for every project: a sequence of ``(filename, content)`` per project,
+        any files, in the caller's order. Equal to ``projects.Project(files)`` per project."""
+        thr = config.confidence_threshold() if threshold is None else threshold
+        return self._score_projects(self._prep_projects(projects), thr, k_licenses)
+
+    def detect_projects_stream(self, batches: Iterable[Sequence[Sequence[Tuple[str, Union[str, bytes]]]]],
+                               threshold=None, k_licenses: int = 4) -> Iterator[List[ProjectDetection]]:
+        """detect_projects() over a stream of batches of projects, as detect_stream's two-stage
+        pipeline: the host prepares batch k + 1 while batch k is on the device. Yields one list per
+        batch, in order, each equal to detect_projects() of that batch."""
+        from concurrent.futures import ThreadPoolExecutor
+        thr = config.confidence_threshold() if threshold is None else threshold
+        it = iter(batches)
+        with ThreadPoolExecutor(1) as ex:
+            nxt = next(it, None)
+            fut = ex.submit(self._prep_projects, nxt) if nxt is not None else None
+            while fut is not None:
+                prepped = fut.result()
+                nxt = next(it, None)
+                fut = ex.submit(self._prep_projects, nxt) if nxt is not None else None
+                yield self._score_projects(prepped, thr, k_licenses)
+
+    def _prep_projects(self, projects):
+        """Host stage of detect_projects: Project#find_files per project (project.rb:111-117: name
+        scores, files that score 0 dropped, score descending -- stably, the caller's order within a
+        score), all license files of all projects as one flat batch through _prep, and per file the
+        name bits of dice_batch_projects' file_flags."""
+        import numpy as np
+        from .project_files import LicenseFile, is_copyright_file
+        if self.exact_on != 'device':
+            raise ValueError("detect_projects reduces the device's resident Exact results: it needs exact_on='device'")
+        # per file only list comprehensions and a dictionary lookup; the select, the stable sort and
+        # the offsets are array operations over the whole batch
+        flat = [f for files in projects for f in files]
+        names = [f[0] for f in flat]
+        known = self._name_info      # filename -> (name score, name bits)
+        if len(known) > (1 << 16):
+            known.clear()
+        for nm in set(names).difference(known):
+            known[nm] = (LicenseFile.name_score(nm),
+                         (2 if is_copyright_file(nm) else 0) | (4 if LicenseFile.lesser_gpl_score(nm) else 0))
+        info = [known[nm] for nm in names]
+        n_all = len(flat)
+        score = np.fromiter((e[0] for e in info), np.float64, n_all)
+        bits = np.fromiter((e[1] for e in info), np.uint8, n_all)
+        sizes = np.fromiter((len(files) for files in projects), np.int64, len(projects))
+        pid = np.repeat(np.arange(len(projects)), sizes)
+        keep = np.flatnonzero(score > 0)
+        order = keep[np.lexsort((-score[keep], pid[keep]))]      # (a stable sort: project, then score descending)
+        offsets = np.zeros(len(projects) + 1, np.int64)
+        np.cumsum(np.bincount(pid[keep], minlength=len(projects)), out=offsets[1:])
+        if order.size == n_all and np.array_equal(order, np.arange(n_all)):
+            contents = [f[1] for f in flat]     # (nothing dropped, nothing moved)
+        else:
+            order_l = order.tolist()
+            names = [names[i] for i in order_l]
+            contents = [flat[i][1] for i in order_l]
+            bits = bits[order]
+        return self._prep(contents, names), names, offsets, bits
+
+    def _template_flags(self):
+        """dice_batch_projects' template_flags: bit 0 License#gpl?, bit 1 #lgpl? (license.rb:200-206)."""
+        import numpy as np
+        if getattr(self, '_tflags', None) is None:
+            self._tflags = np.fromiter(((1 if l.gpl() else 0) | (2 if l.lgpl() else 0) for l in self.engine.templates),
+                                       np.uint8, len(self.engine.templates))
+        return self._tflags
+
+    def _score_projects(self, prepped, thr, k) -> List[ProjectDetection]:
+        """Device stage of detect_projects: the flat batch's upload / Exact / match as detect() runs
+        them, the project reduction on their resident results, and one record per project back."""
+        import numpy as np
+        inner, names, offsets, bits = prepped
+        if inner[0] == 'text':
+            b = self._resident_text(inner)
+            copyright = inner[1][5]
+        else:
+            fb, copyright, third = inner
+            b = self._device_batch(max(fb.n, 1))
+            b.upload(fb)
+            b.exact(third)
+        b.match(float(thr), confidence=True)
+        self.host_hashed = 0
+        flags = (np.asarray(copyright).astype(np.uint8) & 1) | bits
+        b.projects(offsets, flags, self._template_flags(), use_exact=True, k=k)
+        lic, mf, nl, lst = b.download_projects()
+        mt, cf, dg = b.download_project_match(digest=self.content_hash)
+        templates = self.engine.templates
+        tab = list(templates) + [License.find('other'), License.find('no-license'), None]    # (-1: nil)
+        matcher_names = ('copyright', 'exact', 'dice', None)
+        hx = dg.tobytes().hex() if dg is not None else None
+        sizes = np.diff(offsets).tolist()
+        import gc
+        paused = gc.isenabled()
+        gc.disable()     # (as _detections)
+        try:
+            out = []
+            for p, (l, f, m, c, row, cnt, sz) in enumerate(zip(lic.tolist(), mf.tolist(), mt.tolist(), cf.tolist(),
+                                                               lst.tolist(), nl.tolist(), sizes)):
+                out.append(ProjectDetection(
+                    tab[l], names[f] if f >= 0 else None, matcher_names[m],
+                    (c if m == 2 else 100) if m >= 0 else None,
+                    [tab[x] for x in row if x >= 0], cnt, sz,
+                    hx[40 * p:40 * p + 40] if hx is not None and f >= 0 else None))
+            return out
+        finally:
+            if paused:
+                gc.enable()
+
     def _prep(self, contents, filenames=None):
         """Host stage (liblicensee_host.so threads; ctypes releases the GIL during the call)."""
         if self.wordset_on == 'device':
@@ -148,6 +278,18 @@ class BatchDetector:
         """Device stage of wordset_on='device': upload the normalized texts (the device scans and
         interns the wordsets), patch the rare files whose distinct non-vocabulary words overflow
         the device set with host-prepared rows, then Exact + Dice#match/#confidence."""
+        _, (text, off, tl, ln, cc, copyright, _), contents, filenames = prepped
+        b = self._resident_text(prepped)
+        b.match(float(thr), confidence=True)
+        exact = b.download_exact()
+        best, _, score = b.download_match()
+        self.host_hashed = 0
+        hashes = self._hashes(b, contents, filenames) if self.content_hash else None
+        return copyright, exact, best, score, hashes
+
+    def _resident_text(self, prepped):
+        """The texts of a wordset_on='device' batch made resident: upload and scan, the content hash
+        when asked for, host-prepared rows for the files the device scan flagged, and Exact."""
         import numpy as np
         _, (text, off, tl, ln, cc, copyright, _), contents, filenames = prepped
         n = len(off)
@@ -162,12 +304,7 @@ class BatchDetector:
             fb, _, fm, _ = self.host.prep_files(sub, sfn, nthreads=self.nthreads, field_masks=True)
             b.set_rows(over, fb.bits, fb.wordset_size, fm)
         b.exact(None)
-        b.match(float(thr), confidence=True)
-        exact = b.download_exact()
-        best, _, score = b.download_match()
-        self.host_hashed = 0
-        hashes = self._hashes(b, contents, filenames) if self.content_hash else None
-        return copyright, exact, best, score, hashes
+        return b
 
     def _hashes(self, b, contents, filenames) -> List[str]:
         """content_hash per file as hex: the device digests, and for the files the device flagged

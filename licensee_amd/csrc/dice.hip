@@ -541,7 +541,9 @@ void dice_batch_destroy(dice_batch* b) {
     void* ptrs[] = {b->d_rows, b->d_tiles, b->d_wf,  b->d_len,    b->d_cc,    b->d_best,  b->d_ov,   b->d_score,
                     b->d_mov,  b->d_mscore, b->d_tki, b->d_tks, b->d_stage, b->d_pdense, b->d_ids, b->d_offs,
                     b->d_defer, b->d_ndefer, b->d_nscored, b->d_exact, b->d_fmask, b->d_text, b->d_toff,
-                    b->d_tlen, b->d_wstat, b->d_wcnt, b->d_hdig, b->d_hstat, b->d_hcnt};
+                    b->d_tlen, b->d_wstat, b->d_wcnt, b->d_hdig, b->d_hstat, b->d_hcnt,
+                    b->d_poffs, b->d_pfflags, b->d_ptflags, b->d_pdig, b->d_plic, b->d_pmf, b->d_pnl, b->d_plist,
+                    b->d_pmatcher, b->d_pconf};
     for (void* p : ptrs)
         if (p) (void)hipFree(p);
     delete b;
@@ -589,6 +591,7 @@ int dice_batch_upload(dice_batch* b, const dice_files* f, void* stream) {
     b->n_long = 0;
     b->fmask_device = false;
     b->text_state = 0;
+    ++b->epoch;
     b->text_utf8 = false;
     if (n == 0) return DICE_OK;
     HIP_TRY(hipMemcpyAsync(b->d_rows, f->bits, (size_t)n * c->w64 * 8, hipMemcpyHostToDevice, s));
@@ -606,6 +609,7 @@ int dice::upload_rows_resident(dice_batch* b, const dice_files* f, hipStream_t s
     b->n_long = 0;
     b->fmask_device = false;
     b->text_state = 0;
+    ++b->epoch;
     b->text_utf8 = false;
     if (b->n == 0) return DICE_OK;
     return upload_tail(b, b->n, f->wordset_size, f->length, f->cc_false_positive, s);
@@ -633,6 +637,7 @@ int dice_batch_upload_ids(dice_batch* b, int64_t n, const int64_t* offsets, cons
     b->n_long = 0;
     b->fmask_device = false;
     b->text_state = 0;
+    ++b->epoch;
     b->text_utf8 = false;
     if (n == 0) return DICE_OK;
     const size_t need = (size_t)std::max<int64_t>(offsets[n], 1) * (size_t)id_bytes;
@@ -680,8 +685,10 @@ __global__ __launch_bounds__(256) void dice_confidence_outputs(const int32_t* __
 static int batch_match(dice_batch* b, double thr, void* stream, bool confidence) {
     if (!b) return fail(DICE_E_ARG, "NULL batch");
     dice_ctx* c = b->ctx;
+    b->match_epoch = 0;
     if (b->n == 0) {
         b->last_match = 1;   // every pair of the empty batch scored: n * T = 0, nothing deferred
+        b->match_epoch = b->epoch;
         return DICE_OK;
     }
     DeviceGuard g(c->device);
@@ -715,6 +722,7 @@ static int batch_match(dice_batch* b, double thr, void* stream, bool confidence)
                            b->d_ov, b->d_score, b->n);
         HIP_TRY(hipGetLastError());
     }
+    b->match_epoch = b->epoch;
     return DICE_OK;
 }
 

@@ -165,7 +165,9 @@ int dice_batch_exact(dice_batch* b, const uint64_t* file_field_mask, void* strea
     int rc;
     if (!b->d_exact && (rc = dice::dalloc_bytes((void**)&b->d_exact, (size_t)b->capacity * 4))) return rc;
     if (!b->d_fmask && (rc = dice::dalloc_bytes((void**)&b->d_fmask, (size_t)b->capacity * 8))) return rc;
+    b->exact_epoch = b->epoch;
     if (b->n == 0) return DICE_OK;
+    b->exact_epoch = 0;
     hipStream_t s = dice::stream_of(c, stream);
     if (file_field_mask &&
         hipMemcpyAsync(b->d_fmask, file_field_mask, (size_t)b->n * 8, hipMemcpyHostToDevice, s) != hipSuccess)
@@ -177,7 +179,9 @@ int dice_batch_exact(dice_batch* b, const uint64_t* file_field_mask, void* strea
                        (const uint64_t*)b->d_rows, b->n, c->w64, (const uint32_t*)b->d_wf,
                        masks ? (const uint64_t*)b->d_fmask : nullptr, (const uint4*)c->d_ex_tbl,
                        (const uint64_t*)c->d_ex_need, (const uint4*)c->d_ex_rec, c->T, b->d_exact);
-    return hipGetLastError() == hipSuccess ? DICE_OK : fail(DICE_E_DEVICE, "dice_exact_kernel launch failed");
+    if (hipGetLastError() != hipSuccess) return fail(DICE_E_DEVICE, "dice_exact_kernel launch failed");
+    b->exact_epoch = b->epoch;
+    return DICE_OK;
 }
 
 int dice_batch_download_exact(dice_batch* b, int32_t* exact, void* stream) {

@@ -220,6 +220,20 @@ struct dice_batch {
     uint8_t* d_hdig = nullptr;      // [capacity][20] SHA-1 digests
     uint8_t* d_hstat = nullptr;     // [capacity] 1 = one-byte-per-character text with a byte >= 0x80
     uint32_t* d_hcnt = nullptr;     // the kernel's next-file counter
+    // What has run since the last upload: every upload starts a new epoch, and a match, Exact or
+    // project call records the epoch it ran in (dice_batch_projects reads the results of the first two)
+    uint32_t epoch = 1, match_epoch = 0, exact_epoch = 0, proj_epoch = 0;
+    // dice_batch_projects (dice_project.hip): its inputs on the device (offsets [proj_cap + 1], file
+    // flags [capacity], template flags [T]) and one record per project -- license, matched file,
+    // distinct licenses, their first proj_k ([P][proj_k]), the matched file's matcher, confidence
+    // and digest -- allocated on the first call and grown with the project count
+    int64_t proj_cap = 0, proj_P = 0;
+    int32_t proj_k = 0;
+    bool proj_hash = false;         // the last resolve gathered the digests of dice_batch_content_hash
+    int64_t* d_poffs = nullptr;
+    uint8_t *d_pfflags = nullptr, *d_ptflags = nullptr, *d_pdig = nullptr;
+    int32_t *d_plic = nullptr, *d_pmf = nullptr, *d_pnl = nullptr, *d_plist = nullptr, *d_pmatcher = nullptr;
+    double* d_pconf = nullptr;
     // small-call batch: d_wf/d_len/d_cc/d_rows carved from d_in, results from d_out
     void *d_in = nullptr, *d_out = nullptr;
 };

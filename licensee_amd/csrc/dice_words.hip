@@ -883,6 +883,7 @@ static int upload_text(dice_batch* b, bool utf8, int64_t n, const uint8_t* text,
     if (!b->d_fmask && (rc = dice::grow(&b->d_fmask, dummy, cap8))) return rc;
     b->n = n;
     b->n_long = 0;
+    ++b->epoch;
     b->text_state = n == 0;   // (dice_batch_content_hash: the texts are resident once this call succeeds)
     b->text_utf8 = utf8;
     if (n_overflow) *n_overflow = 0;
