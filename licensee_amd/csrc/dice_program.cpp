@@ -222,6 +222,8 @@ int program_launch_topk(dice_ctx* c, dice_batch* b, int32_t k, hipStream_t s) {
 
 }  // namespace dice
 
+static_assert(dice::kProgramMaxTemplates <= dice::kMaxIndexedTemplates, "the match kernels' index byte");
+
 // The exports' argument check; `any_size` also takes corpora of more templates than the program serves.
 static bool templates_ok(const dice_templates* t, bool any_size = false) {
     return t && t->n_templates >= 1 && t->n_vocab >= 1 && t->lf_bits && (any_size || t->n_templates <= dice::kProgramMaxTemplates);

@@ -18,7 +18,7 @@
 //
 // By default the program runs over the compact tile (derive_layout below):
 // words that belong to exactly the same templates are interchangeable for every overlap, so a
-// large class of them is a byte count (v_and_b32 literal + v_sad_u8) instead of bits, and the
+// large class of them is a byte count (one v_dot4_u32_u8 per template and count dword) instead of bits, and the
 // file's tile is half as long. ProgramOptions::compact = false keeps the full-bitset tile. Where it
 // pays (plan_mfma), the module also holds the match kernel with the bit region scored on the matrix
 // cores (kMfmaPrelude); ProgramOptions::match overrides the rule.
@@ -144,7 +144,9 @@ void build_compact_entries(const dice_templates* t, const std::vector<uint64_t>&
     }
 }
 
-// VALU instructions of an entry: v_and_b32 (not for a full mask) + v_bcnt_u32_b32 / v_sad_u8.
+// VALU instructions of an entry: v_and_b32 (not for a full mask) + v_bcnt_u32_b32. A count dword's
+// entry is one v_dot4_u32_u8 now but keeps the weight it had as v_and_b32 + v_sad_u8: the layout
+// choice and the slot order rest on these weights and stay what they were.
 int entry_cost(const Entry& e) { return e.mask == 0xFFFFFFFFu ? 1 : 2; }
 
 // Layout for the corpus and its entries: the class-size threshold that gives the fewest tile quads,
@@ -585,23 +587,25 @@ __device__ __forceinline__ i32 dn(i32 base, i32 slack, i32 tlen, u32 wf, i32 lf)
     return base + (i32)wf + (i32)(adj >> 2);
 }
 __device__ __forceinline__ double sc(u32 o, i32 d) { return ((double)o * 200.0) / (double)d; }
-// Overlaps may carry a template index in bits 24-31 (match kernel): only bits 0-23 count.
+// A fast-path denominator (< 2^21) may carry a template index in bits 24-31 (match kernels): only
+// bits 0-23 count there. The IEEE-double path takes whole 32-bit denominators.
 template <bool FAST>
 __device__ __forceinline__ bool ge(u32 oa, i32 da, u32 ob, i32 db) {
     if (FAST) {
 #if NARROW_MUL
         // ov < 2^11 and den < 2^21: both products < 2^32, full-rate 24-bit multiplies are exact
+        // (v_mul_u32_u24 reads bits 0-23 of either operand)
         return mul24(oa, (u32)db) >= mul24(ob, (u32)da);
 #else
-        return (u64)(oa & 0xFFFFFFu) * (u64)(u32)db >= (u64)(ob & 0xFFFFFFu) * (u64)(u32)da;
+        return (u64)oa * (u64)((u32)db & 0xFFFFFFu) >= (u64)ob * (u64)((u32)da & 0xFFFFFFu);
 #endif
     }
-    return sc(oa & 0xFFFFFFu, da) >= sc(ob & 0xFFFFFFu, db);
+    return sc(oa, da) >= sc(ob, db);
 }
 )HIP";
 
-// Compact tile only: masked four-byte sum of a count dword (v_and_b32 literal + v_sad_u8 against
-// 0, accumulating); the plain-C form serves the host tests.
+// Compact tile only: masked four-byte sum of a count dword. The device program (acc_block) does it
+// in one v_dot4_u32_u8 against a 0/1-per-byte selector; the plain-C form serves the host tests.
 const char* kCompactPrelude = R"HIP(
 #ifndef __HIP_DEVICE_COMPILE__
 __device__ __forceinline__ u32 bytesum(u32 x) { return (x & 0xffu) + ((x >> 8) & 0xffu) + ((x >> 16) & 0xffu) + (x >> 24); }
@@ -618,29 +622,38 @@ __device__ __forceinline__ u32 bytesum(u32 x) { u32 r; asm("v_sad_u8 %0, %1, 0, 
 // kernel only requests the byte there, pins the scalar loads, and forms the flag below its stage
 // (MFMA_SCALARS_REQUESTED, MFMA_SCALARS_USED).
 const char* kMatchKernel = R"HIP(
-// running best: bo = template index << 24 | overlap (0xFF: none yet), bd = its denominator
-#define MATCH_CC const bool cc = ccp[file] != 0;
+// Running best: bo = its overlap, bd = its denominator, bi = its template index. On the fast path
+// (denominators < 2^21) the index rides in bd's top byte, where the denominator's last add puts it
+// for free and the 24-bit multiplies of the compare do not look: one select moves index and
+// denominator together, "none yet" is bd = 0xFF000001 with bo = 0 (any candidate is >= 0 / 1), and
+// bi comes out of bd behind the last template. The IEEE-double path, whose denominators take all
+// 32 bits, keeps bi beside them. AT(p) is the lane's element of a per-file array, IN_RANGE whether
+// the lane has a file: each kernel defines both.
+#define MATCH_CC const bool cc = *AT(ccp) != 0;
 #define MATCH_FILE(PROLOGUE, CC_ABOVE, CC_BELOW) \
-    u32 wf = wfp[file]; \
-    i32 lf = lenp[file]; \
+    u32 wf = *AT(wfp); \
+    i32 lf = *AT(lenp); \
     CC_ABOVE \
     PROLOGUE \
     CC_BELOW \
     const bool fast = CORPUS_FAST && wf < (1u << 20) && lf >= 0 && lf < (1 << 21); \
-    u32 bo = 0xFF000000u; i32 bd = 1; \
+    u32 bo = 0; i32 bd = (i32)0xFF000001u; i32 bi = -1; \
     if (__all(fast)) { \
         MATCH_BODY(true) \
+        bi = ((u32)bd >> 24) == 0xFFu ? -1 : (i32)((u32)bd >> 24); \
+        bd &= 0xFFFFFF; \
     } else { \
+        bd = 1; \
         MATCH_BODY(false) \
     } \
-    if (file < n) { \
-        const i32 bi = (bo >> 24) == 0xFFu ? -1 : (i32)(bo >> 24); \
-        const u32 bov = bo & 0xFFFFFFu; \
-        const double s = bi >= 0 ? sc(bov, bd) : 0.0; \
-        MSTORE(best_out + file, (bi >= 0 && s >= thr) ? bi : -1); \
-        MSTORE(ov_out + file, bov); \
-        MSTORE(score_out + file, s); \
+    if (IN_RANGE) { \
+        const double s = bi >= 0 ? sc(bo, bd) : 0.0; \
+        MSTORE(AT(best_out), (bi >= 0 && s >= thr) ? bi : -1); \
+        MSTORE(AT(ov_out), bo); \
+        MSTORE(AT(score_out), s); \
     }
+#define AT(p) ((p) + file)
+#define IN_RANGE (file < n)
 extern "C" __global__ __launch_bounds__(64 * WPB) void dice_prog_match(
     const uint4* __restrict__ files, i64 n, const u32* __restrict__ wfp, const i32* __restrict__ lenp,
     const unsigned char* __restrict__ ccp, double thr, i32* __restrict__ best_out,
@@ -666,6 +679,8 @@ extern "C" __global__ __launch_bounds__(64 * WPB) void dice_prog_match(
     }
 #endif
 }
+#undef AT
+#undef IN_RANGE
 )HIP";
 
 // Matrix kernel template: KM is the compile-time top-k slot count (4 or 16). MROWS 1 is the matrix
@@ -793,49 +808,68 @@ __device__ __forceinline__ v8i frag8(uint4 v) {
 // loop, it guards against one compiler's folding and hoisting: tests/test_gpu_prog_mfma.py fails on
 // every file with a bit set if either stops working.
 #define MFMA44(a, b, c) __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(a, b, c, 4, 4, 0, ms_, 0, ms_)
-// acc[TA] += overlaps of template TA, acc[TB] += of template TB (rows g and g + 4 of the block),
-// lane = file: lanes 32-63 of the m = 0 register swap with lanes 0-31 of the m = 1 register
+// acc[TA] = overlaps of template TA, acc[TB] = of template TB (rows g and g + 4 of the block),
+// lane = file: lanes 32-63 of the m = 0 register swap with lanes 0-31 of the m = 1 register. The
+// fold writes the accumulators (a template is folded at most once; one of a block without a live
+// fragment keeps its 0) and the count entries behind it add to them.
 #define MFMA_FOLD2(C0, C1, G, TA, TB) { typedef u32 u32x2_ __attribute__((ext_vector_type(2))); \
     const u32x2_ r_ = __builtin_amdgcn_permlane32_swap((u32)C0[G], (u32)C1[G], false, false); \
-    acc[TA] += r_[0]; acc[TB] += r_[1]; }
+    acc[TA] = r_[0]; acc[TB] = r_[1]; }
 #define MFMA_FOLD1(C0, C1, G, TA) { typedef u32 u32x2_ __attribute__((ext_vector_type(2))); \
     const u32x2_ r_ = __builtin_amdgcn_permlane32_swap((u32)C0[G], (u32)C1[G], false, false); \
-    acc[TA] += r_[0]; }
+    acc[TA] = r_[0]; }
 #define MFMA_FOLD1B(C0, C1, G, TB) { typedef u32 u32x2_ __attribute__((ext_vector_type(2))); \
     const u32x2_ r_ = __builtin_amdgcn_permlane32_swap((u32)C0[G], (u32)C1[G], false, false); \
-    acc[TB] += r_[1]; }
+    acc[TB] = r_[1]; }
 // The compiler sinks a load to its first use when nothing holds it: the scheduling barriers keep
 // the tile's loads where the text has them, and the scalars pass through an empty asm below the
 // stage, so that their first use (cc != 0 is a compare the compiler would otherwise do at once,
 // behind a wait that drains the whole load queue) stays below it.
 #define MFMA_PIN __builtin_amdgcn_sched_barrier(0);
-#define MFMA_SCALARS_REQUESTED u32 ccr_ = ccp[file]; MFMA_PIN
+#define MFMA_SCALARS_REQUESTED u32 ccr_ = *AT(ccp); MFMA_PIN
 #define MFMA_SCALARS_USED asm volatile("" : "+v"(wf), "+v"(lf), "+v"(ccr_)); const bool cc = ccr_ != 0;
+// Addresses: a tile's base is wave-uniform and lives on the scalar unit; a lane adds a 32-bit byte
+// offset that does not change from tile to tile (its file's place in a quad, a count quad or a
+// per-file array), so every load and store of the loop is scalar base + vector offset + immediate.
+// The compiler selects that form only where it sees the offset widened next to the access: left
+// alone it widens the offsets once above the loop, or carries whole per-lane pointers around it,
+// and pays 64-bit vector adds per tile. So each offset passes through an empty asm, in place, in
+// the block that uses it (MFMA_QPIN per tile, AT per access): no instruction, one register each.
+#define MFMA_AT(base, off) ((const uint4*)((const char*)(base) + (off)))
+#define MFMA_ELEM(p, off) ({ asm volatile("" : "+v"(off)); (decltype(p))((char*)((p) + tile * 64) + (off)); })
 // Workgroup head: the workgroup's share of the tiles and the wave's first tile, whose quads are
 // requested before the template fragments go into LDS and fly during the fill (a wave without a
 // tile asks for tile 0, which every launch has, helps with the fill and leaves)
 #define MFMA_HEAD \
     __shared__ uint4 tfrag[MFMA_FRAGS * 64]; \
-    const int lane = threadIdx.x & 63; \
+    const u32 lane = threadIdx.x & 63; \
     const i64 nt_ = (n + 63) >> 6; \
-    const i64 t1 = nt_ * (i64)(blockIdx.x + 1) / (i64)gridDim.x; \
+    const i64 t1v_ = nt_ * (i64)(blockIdx.x + 1) / (i64)gridDim.x;   /* 64-bit division: vector registers */ \
+    const i64 t1 = (i64)(((u64)(u32)__builtin_amdgcn_readfirstlane((int)(t1v_ >> 32)) << 32) | \
+                         (u32)__builtin_amdgcn_readfirstlane((int)t1v_)); \
     i64 tile = nt_ * (i64)blockIdx.x / (i64)gridDim.x + __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)); \
+    u32 l1_ = lane, l4_ = lane * 4u, l8_ = lane * 8u, l16_ = lane * 16u, ll_ = lane; \
     MFMA_QDECL \
-    { const uint4* nq_ = files + (tile < t1 ? tile : 0) * (i64)(WQ * 64) + (lane & 31); MFMA_PIN MFMA_QLOAD MFMA_PIN } \
+    { const uint4* nb_ = files + (tile < t1 ? tile : 0) * (i64)(WQ * 64); MFMA_PIN MFMA_QLOAD MFMA_PIN } \
     for (int i = threadIdx.x; i < MFMA_FRAGS * 64; i += 64 * MWK) tfrag[i] = ((const uint4*)dice_mfma_frag)[i]; \
     __syncthreads(); \
     if (tile >= t1) return; \
     int ms_ = 0x7F7F7F7F; asm volatile("" : "+v"(ms_));
-// Per tile: the quads of the wave's next tile. After its last tile a wave has none: the lane
-// offsets collapse (MFMA_NEXT) and the requests, which keep their place so that the loop has one
-// shape and one count of loads in flight, all fall on the 1 KiB of this tile's first quad.
+// Per tile: the quads of the wave's next tile (MFMA_NEXT). After its last tile a wave has none:
+// the requests, which keep their place so that the loop has one shape and one count of loads in
+// flight, then go to tile 0, which every launch has and every such wave shares.
 #define MFMA_TILE \
-    const i64 file = tile * 64 + lane; \
-    const uint4* fp = files + tile * (i64)(WQ * 64) + lane; \
-    const bool more_ = tile + MWK < t1; \
-    const uint4* nq_ = files + (more_ ? tile + MWK : tile) * (i64)(WQ * 64) + (lane & 31); \
-    int ll_ = lane; asm volatile("" : "+v"(ll_));   /* fragment reads stay in the loop (and out of scratch) */
-#define MFMA_NEXT(o) (nq_ + (more_ ? (o) : 0))
+    const uint4* fb_ = files + tile * (i64)(WQ * 64); \
+    const uint4* nb_ = files + (rem_ > MWK ? tile + MWK : 0) * (i64)(WQ * 64); \
+    const u32 left_ = tile + 1 != nt_ ? 64u : (u32)(n - tile * 64); \
+    MFMA_QPIN asm volatile("" : "+v"(l16_), "+v"(ll_));   /* ll_ opaque: fragment reads stay in the loop (and out of scratch) */
+#define MFMA_NEXT(o) MFMA_AT(nb_, o)
+// The lane's element of a per-file array: the tile's part of it (scalar) + the lane offset for the
+// element size (l1_, l4_, l8_ of MFMA_HEAD; there is none for other sizes).
+#define AT(p) ({ \
+    static_assert(sizeof(*(p)) == 1 || sizeof(*(p)) == 4 || sizeof(*(p)) == 8, "AT: no lane offset for this element size"); \
+    sizeof(*(p)) == 1 ? MFMA_ELEM(p, l1_) : sizeof(*(p)) == 4 ? MFMA_ELEM(p, l4_) : MFMA_ELEM(p, l8_); })
+#define IN_RANGE (l1_ < left_)
 )HIP";
 
 const char* kMatchKernelMfma = R"HIP(
@@ -844,9 +878,13 @@ extern "C" __global__ __launch_bounds__(64 * MWK) void dice_prog_match_mfma(
     const unsigned char* __restrict__ ccp, double thr, i32* __restrict__ best_out,
     u32* __restrict__ ov_out, double* __restrict__ score_out) {
     MFMA_HEAD
-    for (; tile < t1; tile += MWK) {
+    // rem_: the tiles from this one to the end of the workgroup's share (>= 1 here). The scalar unit
+    // has no ordered 64-bit compare, so the loop counts in 32 bits; a share of 2^32 tiles is beyond
+    // any memory.
+    for (u32 rem_ = (u32)(t1 - tile);; rem_ -= MWK, tile += MWK) {
         MFMA_TILE
         MATCH_FILE(FILE_PROLOGUE_MFMA, MFMA_SCALARS_REQUESTED, MFMA_SCALARS_USED)
+        if (rem_ <= MWK) break;
     }
 }
 )HIP";
@@ -912,13 +950,25 @@ std::string acc_stmt(const Entry& en) {
 // A block of dword-major accumulations (entries of one quad) as ONE asm statement: the hazard
 // recognizer pads every inline-asm boundary with an s_nop, so per-entry asm would cost an
 // s_nop per v_and/v_bcnt pair. ACC_C_ONLY carries the plain-C form (host tests, ACC_ASM=0).
-std::string acc_block(const std::vector<Entry>& dm, size_t b, size_t e) {
+// An entry of a count dword is one v_dot4_u32_u8 (acc += sum of byte x selector byte) against the
+// mask's 0/1-per-byte selector, a scalar operand: VOP3P takes no literal on gfx950.
+// Hazard, kept here because the compiler's recognizer does not look inside an asm statement: on
+// gfx950 a VALU instruction other than a dot that reads or writes the destination of a v_dot4 must
+// follow it by at least kDotWait wait states (a dot accumulating on a dot needs none). Inside a block
+// an s_nop goes in front of such an instruction where other instructions do not fill the distance;
+// with `pad_end` (the block's successor is not known to be dots alone) the block ends far enough
+// behind its last dots for whatever follows the statement.
+constexpr int kDotWait = 3;
+std::string acc_block(const std::vector<Entry>& dm, size_t b, size_t e, bool pad_end) {
     std::vector<int32_t> tpls;
     std::vector<int> fk;
+    std::vector<uint32_t> sels;
     for (size_t i = b; i < e; ++i) {
         if (std::find(tpls.begin(), tpls.end(), dm[i].tpl) == tpls.end()) tpls.push_back(dm[i].tpl);
         const int k = dm[i].dword % 4;
         if (std::find(fk.begin(), fk.end(), k) == fk.end()) fk.push_back(k);
+        const uint32_t sel = dm[i].mask & 0x01010101u;
+        if (dm[i].sum && std::find(sels.begin(), sels.end(), sel) == sels.end()) sels.push_back(sel);
     }
     auto acc_op = [&](int32_t tpl) { return (int)(std::find(tpls.begin(), tpls.end(), tpl) - tpls.begin()); };
     // 4 temporaries: the v_and of up to 4 entries issue back to back, then their v_bcnt, so
@@ -926,41 +976,60 @@ std::string acc_block(const std::vector<Entry>& dm, size_t b, size_t e) {
     constexpr int kTmp = 4;
     const int tmp0 = (int)tpls.size();
     auto f_op = [&](int k) { return tmp0 + kTmp + (int)(std::find(fk.begin(), fk.end(), k) - fk.begin()); };
+    auto sel_op = [&](uint32_t mask) {
+        return tmp0 + kTmp + (int)fk.size() + (int)(std::find(sels.begin(), sels.end(), mask & 0x01010101u) - sels.begin());
+    };
     std::ostringstream a, c;
     a << "ACC_ASM_ONLY(asm(\"";
     bool first = true;
+    int pos = 0;                                     // wait states issued so far in this block
+    std::vector<int> dot_at(tpls.size(), -kDotWait - 1);   // per accumulator: where its last dot was issued
     auto emit = [&](const std::string& ins) {
         if (!first) a << "\\n\\t";
         a << ins;
         first = false;
     };
+    auto wait_for = [&](int gap) {                   // s_nop N stands for N + 1 wait states
+        if (gap <= 0) return;
+        emit("s_nop " + std::to_string(gap - 1));
+        pos += gap;
+    };
     for (size_t g = b; g < e; g += kTmp) {
         const size_t ge = std::min(e, g + kTmp);
         for (size_t i = g; i < ge; ++i) {
             const Entry& en = dm[i];
-            if (en.mask == 0xFFFFFFFFu) continue;
+            if (en.mask == 0xFFFFFFFFu || en.sum) continue;
             std::ostringstream ins;
             ins << "v_and_b32 %" << tmp0 + (int)(i - g) << ", 0x" << std::hex << en.mask << std::dec << ", %"
                 << f_op(en.dword % 4);
             emit(ins.str());
+            ++pos;
         }
         for (size_t i = g; i < ge; ++i) {
             const Entry& en = dm[i];
             std::ostringstream ins;
+            if (en.sum)
+                dot_at[(size_t)acc_op(en.tpl)] = pos;
+            else
+                wait_for(dot_at[(size_t)acc_op(en.tpl)] + 1 + kDotWait - pos);
             const int src = en.mask == 0xFFFFFFFFu ? f_op(en.dword % 4) : tmp0 + (int)(i - g);
             if (en.sum)   // count dword: sum of the selected bytes
-                ins << "v_sad_u8 %" << acc_op(en.tpl) << ", %" << src << ", 0, %" << acc_op(en.tpl);
+                ins << "v_dot4_u32_u8 %" << acc_op(en.tpl) << ", %" << f_op(en.dword % 4) << ", %" << sel_op(en.mask) << ", %"
+                    << acc_op(en.tpl);
             else
                 ins << "v_bcnt_u32_b32 %" << acc_op(en.tpl) << ", %" << src << ", %" << acc_op(en.tpl);
             emit(ins.str());
+            ++pos;
         }
         for (size_t i = g; i < ge; ++i) c << acc_stmt(dm[i]);
     }
+    if (pad_end) wait_for(*std::max_element(dot_at.begin(), dot_at.end()) + 1 + kDotWait - pos);
     a << "\" : ";
     for (size_t i = 0; i < tpls.size(); ++i) a << "\"+v\"(acc[" << tpls[i] << "]), ";
     for (int k = 0; k < kTmp; ++k) a << "\"=&v\"(t_[" << k << "])" << (k + 1 < kTmp ? ", " : "");
     a << " : ";
     for (size_t i = 0; i < fk.size(); ++i) a << (i ? ", " : "") << "\"v\"(f[" << fk[i] << "])";
+    for (uint32_t sel : sels) a << ", \"s\"(0x" << std::hex << sel << std::dec << "u)";
     a << ");)";
     std::string cs = c.str();
     std::replace(cs.begin(), cs.end(), '\n', ' ');
@@ -968,12 +1037,18 @@ std::string acc_block(const std::vector<Entry>& dm, size_t b, size_t e) {
 }
 
 // Accumulations of the entries [b0, end) of the quad in tile slot `slot`, in blocks of at most
-// kAccBlock entries.
+// kAccBlock entries. A block is padded for the dot hazard (acc_block) unless the next block of the
+// quad holds count entries only; what follows the quad's last block is not known here.
 std::string acc_quad(const Program& p, size_t b0, size_t end, size_t slot) {
     constexpr size_t kAccBlock = 4;   // entries per asm block (2 and 8 measured slower)
     if (p.opts.diag == ProgramOptions::kNoAcc) return "acc[" + std::to_string(slot) + " % NT] ^= f[0] ^ f[1] ^ f[2] ^ f[3];\n";
     std::string out;
-    for (size_t b = b0; b < end; b += kAccBlock) out += acc_block(p.sched.dm, b, std::min(end, b + kAccBlock));
+    for (size_t b = b0; b < end; b += kAccBlock) {
+        const size_t be = std::min(end, b + kAccBlock);
+        bool pad_end = be == end;
+        for (size_t i = be; i < std::min(end, be + kAccBlock); ++i) pad_end = pad_end || !p.sched.dm[i].sum;
+        out += acc_block(p.sched.dm, b, be, pad_end);
+    }
     return out;
 }
 
@@ -1014,8 +1089,9 @@ std::string valu_prologue(const Program& p) {
 // lane per file, the live K-steps pair by pair of bit quads (one fragment read and two matrix
 // instructions per live block) with the next tile's pair requested behind them, the fold into acc[]
 // through the row map, then the count entries as in the VALU program. With it the MFMA_QDECL
-// and MFMA_QLOAD macros: per-lane quad offsets (lane half h takes the odd quad of each pair),
-// declarations, loads.
+// and MFMA_QLOAD macros: per-lane byte offsets into a tile (lane half h takes the odd quad of each
+// pair; l16_ is the lane's place in a count quad), declarations, loads from the tile at nb_, and
+// MFMA_QPIN (kMfmaPrelude).
 void emit_mfma_prologue(std::ostringstream& s, const dice_templates* t, const Program& p) {
     const MfmaTables& m = p.mf;
     const std::vector<Entry>& dm = p.sched.dm;
@@ -1028,7 +1104,7 @@ void emit_mfma_prologue(std::ostringstream& s, const dice_templates* t, const Pr
         size_t b = p.sched.range[i].first;
         while (b < p.sched.range[i].second && !dm[b].sum) ++b;
         crange[i] = {b, p.sched.range[i].second};
-        if (b < p.sched.range[i].second) o << "const uint4 cq_" << i << " = ldq(fp + " << i * 64 << ");\n";
+        if (b < p.sched.range[i].second) o << "const uint4 cq_" << i << " = ldq(MFMA_AT(fb_, l16_) + " << i * 64 << ");\n";
     }
     o << "MFMA_PIN\n";   // the count quads are requested here, above the K-steps
     // DICE_PROG_DIAG=nomfma (results wrong): neither fragment reads nor matrix instructions; the
@@ -1086,10 +1162,15 @@ void emit_mfma_prologue(std::ostringstream& s, const dice_templates* t, const Pr
     std::ostringstream qd, ql;
     for (int32_t u = 0; u < np; ++u) {
         const int32_t s0 = m.slots[(size_t)2 * u], s1 = m.slots[(size_t)2 * u + 1] >= 0 ? m.slots[(size_t)2 * u + 1] : s0;
-        qd << "const int o_" << u << " = (lane >> 5) ? " << s1 * 64 << " : " << s0 * 64 << "; uint4 q0_" << u
-           << ", q1_" << u << ";\n";
-        ql << "q0_" << u << " = ldq(nq_ + o_" << u << "); q1_" << u << " = ldq(nq_ + o_" << u << " + 32);\n";
+        qd << "u32 o_" << u << " = (((lane >> 5) ? " << s1 * 64 << "u : " << s0 * 64 << "u) + (lane & 31)) * 16u; uint4 q0_"
+           << u << ", q1_" << u << ";\n";
+        ql << "q0_" << u << " = ldq(MFMA_NEXT(o_" << u << ")); q1_" << u << " = ldq(MFMA_NEXT(o_" << u << ") + 32);\n";
     }
+    std::ostringstream qp;
+    qp << "asm volatile(\"\" : ";
+    for (int32_t u = 0; u < np; ++u) qp << (u ? ", " : "") << "\"+v\"(o_" << u << ")";
+    qp << ");\n";
+    emit_macro(s, "MFMA_QPIN", qp.str());
     emit_macro(s, "MFMA_QDECL", qd.str());
     emit_macro(s, "MFMA_QLOAD", ql.str());
     emit_macro(s, "FILE_PROLOGUE_MFMA", o.str());
@@ -1099,20 +1180,24 @@ void emit_mfma_prologue(std::ostringstream& s, const dice_templates* t, const Pr
 // (match) or to the row and the top-k slots (MOFFER).
 void epilogue_bodies(const dice_templates* t, const Program& p, std::string& match_body, std::string& matrix_body) {
     std::ostringstream mb, xb;
+    // The fast path's index byte (MATCH_FILE) holds indices up to kMaxIndexedTemplates - 1: 0xFF is "none
+    // yet". The literal is formed unsigned, so an index above 127 wraps into a negative i32 whose bits are right.
     for (int32_t i = 0; i < t->n_templates; ++i) {
         const int32_t base = (int32_t)t->lf_size[i] - (int32_t)t->fields_set_size[i];
         std::ostringstream den;
         den << "{ const u32 a = acc[" << i << "]; i32 d; d = dn(" << base << ", " << t->length_slack[i] << ", "
             << t->length[i] << ", wf, lf); ";
-        // a carries the template index in its top byte (ACC_INIT): one select moves index and
-        // overlap together; v_mul_u32_u24 reads only the low 24 bits (the overlap)
-        mb << den.str() << (t->is_cc[i] ? "if (!cc) " : "")
-           << "{ if ((!FASTV && (bo >> 24) == 0xFFu) || ge<FASTV>(a, d, bo, bd)) { bo = a; bd = d; } } }\n";
+        // match, fast path: d carries the template index in its top byte, added with the literal
+        // base (MATCH_FILE); the IEEE-double path keeps whole denominators and bi beside them
+        mb << "{ const u32 a = acc[" << i << "]; const i32 d = dn(FASTV ? " << (int32_t)((uint32_t)base + ((uint32_t)i << 24)) << " : " << base << ", "
+           << t->length_slack[i] << ", " << t->length[i] << ", wf, lf); " << (t->is_cc[i] ? "if (!cc) " : "")
+           << "{ if (FASTV) { if (ge<true>(a, d, bo, bd)) { bo = a; bd = d; } } else if (bi < 0 || ge<false>(a, d, bo, bd)) "
+              "{ bo = a; bd = d; bi = " << i << "; } } }\n";
         xb << den.str() << "MOFFER(" << i << ", " << (t->is_cc[i] ? 1 : 0) << ") }\n";
     }
     match_body = mb.str();
     if (p.opts.diag == ProgramOptions::kNoEpi)
-        match_body = "bd = 1; bo = 0; _Pragma(\"unroll\") for (int i = 0; i < NT; ++i) bo += acc[i];\n";
+        match_body = "bd = 1; bo = 0; bi = 0; _Pragma(\"unroll\") for (int i = 0; i < NT; ++i) bo += acc[i];\n";
     matrix_body = xb.str();
 }
 
@@ -1253,8 +1338,7 @@ std::string emit_program(const dice_templates* t, const Program& p) {
     emit_macro(s, "FILE_PROLOGUE", valu_prologue(p));
     s << "#define WAVE_TIMING " << (p.opts.diag == ProgramOptions::kTiming ? 1 : 0) << "\n";
     emit_macro(s, "MATCH_BODY(FASTV_) { constexpr bool FASTV = FASTV_;", match_body + "}");
-    s << "#define ACC_INIT(i) ((u32)(i) << 24)\n" << kMatchKernel
-      << "#undef ACC_INIT\n#define ACC_INIT(i) 0u\n";
+    s << "#define ACC_INIT(i) 0u\n" << kMatchKernel;
     s << kMatrixOffer;
     emit_macro(s, "MATRIX_BODY(FASTV_) { constexpr bool FASTV = FASTV_;", matrix_body + "}");
     for (int rows : {1, 0}) {
@@ -1272,8 +1356,7 @@ std::string emit_program(const dice_templates* t, const Program& p) {
         for (size_t i = 0; i < p.mf.dfrag.size(); ++i) s << "0x" << p.mf.dfrag[i] << (i % 16 == 15 ? ",\n" : ",");
         s << std::dec << "};\n" << kMfmaPrelude;
         emit_mfma_prologue(s, t, p);
-        s << "#define MWK " << kMfmaMatchWaves << "\n#undef ACC_INIT\n#define ACC_INIT(i) ((u32)(i) << 24)\n" << kMatchKernelMfma
-          << "#undef ACC_INIT\n#define ACC_INIT(i) 0u\n#endif\n";
+        s << "#define MWK " << kMfmaMatchWaves << "\n" << kMatchKernelMfma << "#undef AT\n#undef IN_RANGE\n#endif\n";
     }
     if (p.opts.compact) emit_pack_kernel(s, p, (t->n_vocab + 63) / 64);
     return s.str();

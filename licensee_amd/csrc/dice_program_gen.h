@@ -16,6 +16,7 @@
 namespace dice {
 
 constexpr int32_t kProgramWaves = 4;    // waves (64-file tiles) per workgroup (1, 2 and 8 within +-1.5%)
+constexpr int kMaxIndexedTemplates = 255;   // the match kernels keep the template index in one byte, 0xFF = none yet
 constexpr int kMfmaMatchWaves = 12;     // MWK of the generated matrix-core match kernel
 
 // What the environment may choose (program_options_from_env in dice_program.cpp reads it, at
