@@ -64,7 +64,10 @@ extern "C" {
 typedef struct dice_ctx dice_ctx;
 typedef struct dice_batch dice_batch;
 
-/* One entry per template, in License.all(hidden: true, psuedo: false) key order. */
+/* One entry per template, in License.all(hidden: true, psuedo: false) key order.
+ * Input domain: length >= 0 (a character count) and |Lf| - |fields_normalized_set| >= 1 (with 0 an
+ * empty file scores 0.0 / 0 in the reference); with the files scored against them, every
+ * denominator |Lf| - |Fld| + |W_F| + adjusted length delta / 4 must fit int32. */
 typedef struct dice_templates {
     int32_t n_templates;            /* T (>= 1)                                              */
     int32_t n_vocab;                /* V, bits per bitset (>= 1)                              */
@@ -83,7 +86,9 @@ typedef struct dice_files {
     int64_t n_files;
     const uint64_t *bits;           /* [n][dice_words64(V)] row-major wordset bitsets        */
     const uint32_t *wordset_size;   /* [n] |W_F|: all distinct words, in or out of vocabulary */
-    const int32_t *length;          /* [n] content_normalized.length (characters)            */
+    const int32_t *length;          /* [n] content_normalized.length (characters): >= 0, a     */
+                                    /*     negative length is outside the input domain, as is  */
+                                    /*     a denominator that does not fit int32 (above)       */
     const uint8_t *cc_false_positive; /* [n] potential_false_positive? (license_file.rb:80-82) */
 } dice_files;
 

@@ -17,7 +17,9 @@ __device__ __forceinline__ uint32_t rfl(uint32_t v) { return __builtin_amdgcn_re
 // the rational compare is exact in 24-bit multiplies and equals the double order (dice_common.h).
 template <bool FAST>
 __device__ __forceinline__ bool ge(uint32_t oa, int32_t da, uint32_t ob, int32_t db) {
-    if (FAST) return __umul24(oa, (uint32_t)db) >= __umul24(ob, (uint32_t)da);
+    // (HIP declares __umul24 as returning int: without the casts the compare is signed, and a product
+    // of 2^31 or more -- 2,047 words against a denominator above 2^20 -- ranks below every smaller one)
+    if (FAST) return (uint32_t)__umul24(oa, (uint32_t)db) >= (uint32_t)__umul24(ob, (uint32_t)da);
     return dice_ge(oa, da, ob, db);
 }
 
