@@ -256,7 +256,14 @@ int64_t dice_batch_bytes_per_file(const dice_batch *batch);
  * all zero) holds the same numbering's bits of the file's wordset (lh_prep_files).
  * exact[i] = template index or -1. The kernel reads the batch's row-major bitsets (the
  * stream probe overwrites them). dice_batch_exact is asynchronous on `stream`: the field masks
- * are copied from host memory on that stream, so they must stay valid until it has run. */
+ * are copied from host memory on that stream, so they must stay valid until it has run.
+ * file_field_mask = NULL reads the device's own masks only when the batch's last upload was
+ * dice_batch_upload_text / dice_batch_upload_text_utf8 (as dice_batch_set_rows has patched them
+ * since). After every other upload (dice_batch_upload, dice_batch_upload_ids, the sharded calls'
+ * uploads) NULL means all zero for every file, whatever an earlier call or dice_batch_set_rows left
+ * in the batch's mask buffer: those uploads carry no masks, so no file of the batch has one.
+ * dice_exact_setup may be called again: the new tables replace the old ones for every batch of
+ * the context, resident ones included. */
 int dice_exact_setup(dice_ctx *ctx, const uint32_t *wordset_size, const uint64_t *field_bits,
                      const uint64_t *field_need);
 int dice_batch_exact(dice_batch *batch, const uint64_t *file_field_mask, void *stream);
@@ -303,7 +310,10 @@ int dice_batch_upload_text_utf8(dice_batch *batch, int64_t n_files, const uint8_
  * left them (the caller's, or the device's count); synchronizes `stream`. */
 int dice_batch_download_length(dice_batch *batch, int32_t *length, void *stream);
 /* Overwrite the rows, |W_F| and field masks (NULL: zero) of files index[0..k) of the resident
- * batch (bits: [k][dice_words64(V)]); synchronizes `stream`. */
+ * batch (bits: [k][dice_words64(V)]); synchronizes `stream`. The masks written here are read by
+ * dice_batch_exact(file_field_mask = NULL) only in a batch whose last upload was a text upload,
+ * where every other file has a device mask too; after any other upload that call takes all masks
+ * as zero, these included (pass the whole batch's masks to dice_batch_exact instead). */
 int dice_batch_set_rows(dice_batch *batch, int64_t k, const int64_t *index, const uint64_t *bits,
                         const uint32_t *wordset_size, const uint64_t *field_mask, void *stream);
 /* Page-locked host memory (hipHostMalloc) for upload buffers -- texts, bitsets -- so their H2D

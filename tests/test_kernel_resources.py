@@ -56,6 +56,15 @@ def test_mfma_dense_prefix_kernel_fits_3_waves_without_scratch():
 
 
 @pytest.mark.skipif(not os.path.exists(HIPCC), reason='hipcc not present')
+def test_exact_kernel_runs_without_scratch():
+    """dice_exact_kernel: one lane per file, a dozen live values -- nothing to spill. No occupancy
+    bar: none is documented for this kernel."""
+    res = _resources('dice_exact.hip')
+    r = next(v for k, v in res.items() if k.endswith('dice::dice_exact_kernel'))
+    assert r['ScratchSize [bytes/lane]'] == '0' and r['VGPRs Spill'] == '0', r
+
+
+@pytest.mark.skipif(not os.path.exists(HIPCC), reason='hipcc not present')
 def test_wordset_scan_kernel_fits_4_waves_without_scratch():
     """dice_words_kernel: 4-wave workgroups, four per CU (LDS ~10 KiB per wave), asked for 4 waves
     per SIMD (amdgpu_waves_per_eu) -- no scratch, VGPRs within 4 waves' share."""

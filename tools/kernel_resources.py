@@ -29,7 +29,8 @@ def kernel_resources(src, extra_flags=()):
                 name = subprocess.run(['c++filt', name], capture_output=True, text=True).stdout.strip()
             except OSError:
                 pass
-            cur = {'name': re.sub(r'\(.*', '', name)}
+            # dice::(anonymous namespace)::kernel(args) -> dice::kernel
+            cur = {'name': re.sub(r'\(.*', '', name.replace('(anonymous namespace)::', ''))}
             rows.append(cur)
         elif cur is not None and ':' in txt:
             k, v = txt.split(':', 1)
