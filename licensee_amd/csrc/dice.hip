@@ -241,40 +241,10 @@ __global__ __launch_bounds__(256) void dice_dense_matrix(
 // ---------------------------------------------------------------------------------------
 namespace {
 
-#define HIP_TRY(expr)                                                                          \
-    do {                                                                                       \
-        hipError_t e_ = (expr);                                                                \
-        if (e_ != hipSuccess)                                                                  \
-            return fail(DICE_E_DEVICE, std::string(#expr) + ": " + hipGetErrorString(e_));     \
-    } while (0)
-
 constexpr int kTT = 48;        // templates per dense pass
 constexpr int kBlock = 256;    // 4 waves, one 64-file tile each
 
-struct DeviceGuard {
-    int prev = -1;
-    bool ok = false;
-    explicit DeviceGuard(int dev) {
-        if (hipGetDevice(&prev) != hipSuccess) prev = -1;
-        ok = hipSetDevice(dev) == hipSuccess;
-    }
-    ~DeviceGuard() {
-        if (prev >= 0) (void)hipSetDevice(prev);
-    }
-};
-
-template <class T>
-int dalloc(T** p, size_t count) {
-    *p = nullptr;
-    if (count == 0) count = 1;
-    hipError_t e = hipMalloc((void**)p, count * sizeof(T));
-    if (e != hipSuccess) return fail(DICE_E_NOMEM, std::string("hipMalloc: ") + hipGetErrorString(e));
-    return DICE_OK;
-}
-
 }  // namespace
-
-static hipStream_t pick_stream(dice_ctx* ctx, void* s) { return s ? (hipStream_t)s : ctx->stream; }
 
 // A/B switch read per call (e.g. DICE_NO_SMALL_CALL=1: the small calls take the general path)
 static bool getenv_flag(const char* name) {
@@ -288,15 +258,9 @@ static int transpose_to(dice_batch* b, const E* d_src, int64_t rows, int64_t col
     // rows x cols (template-major) -> cols x rows on device, then a copy to `dst` (host memory,
     // or another device's memory for the sharded device gather)
     const size_t bytes = (size_t)rows * cols * sizeof(E);
-    if (b->stage_bytes < bytes) {
-        if (b->d_stage) (void)hipFree(b->d_stage);
-        b->d_stage = nullptr;
-        b->stage_bytes = 0;
-        if (hipMalloc(&b->d_stage, bytes) != hipSuccess) return fail(DICE_E_NOMEM, "stage alloc");
-        b->stage_bytes = bytes;
-    }
+    if (int rc = b->d_stage.reserve(bytes)) return rc;
     dim3 grid((unsigned)((cols + 63) / 64), (unsigned)((rows + 63) / 64));
-    hipLaunchKernelGGL(dice_transpose<E>, grid, dim3(256), 0, s, d_src, (E*)b->d_stage, rows, cols);
+    hipLaunchKernelGGL(dice_transpose<E>, grid, dim3(256), 0, s, d_src, (E*)b->d_stage.get(), rows, cols);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipMemcpyAsync(dst, b->d_stage, bytes, kind, s));
     HIP_TRY(hipStreamSynchronize(s));
@@ -322,10 +286,7 @@ int dice::upload_tail(dice_batch* b, int64_t n, const uint32_t* wf, const int32_
         HIP_TRY(hipMemsetAsync(b->d_cc + n, 0, (size_t)(npad - n), s));
     }
     if (c->kind == 3) {   // the postings kernel reads the row-major bitsets
-        if (!wf) return DICE_OK;
-        b->n_long = 0;
-        if (c->prune)
-            for (int64_t i = 0; i < n; ++i) b->n_long += wf[i] > c->prune_max_lf;
+        if (wf) b->n_long = count_long(c, wf, n);
         return DICE_OK;
     }
     return dice::repack(b, s);
@@ -364,22 +325,13 @@ static void ctx_free(dice_ctx* c) {
     if (c->small) dice_batch_destroy(c->small);
     if (c->h_small_in) (void)hipHostFree(c->h_small_in);
     if (c->h_small_out) (void)hipHostFree(c->h_small_out);
-    if (c->d_tq) (void)hipFree(c->d_tq);
-    if (c->d_tc) (void)hipFree(c->d_tc);
-    if (c->d_qperm) (void)hipFree(c->d_qperm);
-    void* plan[] = {c->d_lrec, c->d_lep,  c->d_les,  c->d_lwt,   c->d_pdmt,  c->d_prow,  c->d_povf,
-                    c->d_ptc,  c->d_p4q8, c->d_p4tc, c->d_p4cc,  c->d_p4off, c->d_p4rec, c->d_p4slot};
-    for (void* p : plan)
-        if (p) (void)hipFree(p);
     if (c->module) (void)hipModuleUnload(c->module);
     for (int i = 0; i < 2; ++i) {
         if (c->stage_ev[i]) (void)hipEventDestroy(c->stage_ev[i]);
         if (c->h_stage[i]) (void)hipHostFree(c->h_stage[i]);
     }
-    dice::exact_free(c);
-    dice::words_free(c);
     if (c->stream) (void)hipStreamDestroy(c->stream);
-    delete c;
+    delete c;   // the device buffers
 }
 
 // One HIP runtime per process. The library binds libamdhip64.so.7 by soname, so it shares the
@@ -470,7 +422,7 @@ int dice_create(const dice_templates* t, int32_t device, dice_ctx** out) {
         hc[i] = make_int4((int32_t)t->lf_size[i] - (int32_t)t->fields_set_size[i], t->length_slack[i],
                           t->length[i], t->is_cc[i] ? 1 : 0);
     }
-    if ((rc = dalloc(&c->d_tq, hq.size())) || (rc = dalloc(&c->d_tc, hc.size()))) {
+    if ((rc = c->d_tq.reserve(hq.size())) || (rc = c->d_tc.reserve(hc.size()))) {
         ctx_free(c);
         return rc;
     }
@@ -529,46 +481,40 @@ int32_t dice_ctx_match_kernel(const dice_ctx* ctx) {
 void dice_batch_destroy(dice_batch* b) {
     if (!b) return;
     DeviceGuard g(b->ctx->device);
-    if (b->d_in) {   // carved small-call batch: the regions own these
-        b->d_wf = nullptr; b->d_len = nullptr; b->d_cc = nullptr; b->d_rows = nullptr;
-        (void)hipFree(b->d_in);
-    }
-    if (b->d_out) {
-        b->d_best = nullptr; b->d_ov = nullptr; b->d_score = nullptr;
-        b->d_mov = nullptr; b->d_mscore = nullptr; b->d_tki = nullptr; b->d_tks = nullptr;
-        (void)hipFree(b->d_out);
-    }
-    void* ptrs[] = {b->d_rows, b->d_tiles, b->d_wf,  b->d_len,    b->d_cc,    b->d_best,  b->d_ov,   b->d_score,
-                    b->d_mov,  b->d_mscore, b->d_tki, b->d_tks, b->d_stage, b->d_pdense, b->d_ids, b->d_offs,
-                    b->d_defer, b->d_ndefer, b->d_nscored, b->d_exact, b->d_fmask, b->d_text, b->d_toff,
-                    b->d_tlen, b->d_wstat, b->d_wcnt, b->d_hdig, b->d_hstat, b->d_hcnt,
-                    b->d_poffs, b->d_pfflags, b->d_ptflags, b->d_pdig, b->d_plic, b->d_pmf, b->d_pnl, b->d_plist,
-                    b->d_pmatcher, b->d_pconf};
-    for (void* p : ptrs)
-        if (p) (void)hipFree(p);
     delete b;
+}
+
+// What every batch has wherever its inputs and results live: capacity, tiles, the pruned match's buffers.
+static int batch_new(dice_ctx* ctx, int64_t capacity, dice_batch** out) {
+    dice_batch* b = new (std::nothrow) dice_batch();
+    if (!b) return fail(DICE_E_NOMEM, "batch alloc");
+    b->ctx = ctx;
+    b->capacity = capacity;
+    b->n_tiles_cap = (capacity + kWave - 1) / kWave;
+    int rc;
+    if ((rc = b->d_tiles.reserve((size_t)b->n_tiles_cap * ctx->twq * kWave)) ||
+        (ctx->prune && (rc = dice::prune_reserve(ctx, b)))) {
+        delete b;
+        return rc;
+    }
+    *out = b;
+    return DICE_OK;
 }
 
 int dice_batch_create(dice_ctx* ctx, int64_t capacity, dice_batch** out) {
     if (!ctx || !out || capacity < 1) return fail(DICE_E_ARG, "invalid batch arguments");
     *out = nullptr;
     DeviceGuard g(ctx->device);
-    dice_batch* b = new (std::nothrow) dice_batch();
-    if (!b) return fail(DICE_E_NOMEM, "batch alloc");
-    b->ctx = ctx;
-    b->capacity = capacity;
-    b->n_tiles_cap = (capacity + kWave - 1) / kWave;
-    const int64_t npad = b->n_tiles_cap * kWave;
-    int rc;
-    if ((rc = dalloc(&b->d_rows, (size_t)capacity * ctx->w64)) ||
-        (rc = dalloc(&b->d_tiles, (size_t)b->n_tiles_cap * ctx->twq * kWave)) ||
-        (rc = dalloc(&b->d_wf, npad)) || (rc = dalloc(&b->d_len, npad)) || (rc = dalloc(&b->d_cc, npad)) ||
-        (rc = dalloc(&b->d_best, npad)) || (rc = dalloc(&b->d_ov, npad)) || (rc = dalloc(&b->d_score, npad)) ||
-        (ctx->prune && (rc = dice::prune_reserve(ctx, b)))) {
-        dice_batch_destroy(b);
+    dice_batch* b = nullptr;
+    int rc = batch_new(ctx, capacity, &b);
+    if (rc) return rc;
+    const size_t npad = (size_t)b->n_tiles_cap * kWave;
+    if ((rc = b->d_rows.reserve((size_t)capacity * ctx->w64)) || (rc = b->d_wf.reserve(npad)) ||
+        (rc = b->d_len.reserve(npad)) || (rc = b->d_cc.reserve(npad)) || (rc = b->d_best.reserve(npad)) ||
+        (rc = b->d_ov.reserve(npad)) || (rc = b->d_score.reserve(npad))) {
+        delete b;
         return rc;
     }
-
     *out = b;
     return DICE_OK;
 }
@@ -582,17 +528,11 @@ int dice_batch_upload(dice_batch* b, const dice_files* f, void* stream) {
     if (!b || !f) return fail(DICE_E_ARG, "NULL batch/files");
     dice_ctx* c = b->ctx;
     if (f->n_files < 0 || f->n_files > b->capacity) return fail(DICE_E_ARG, "n_files exceeds batch capacity");
-    if (f->n_files > 0 && (!f->bits || !f->wordset_size || !f->length || !f->cc_false_positive))
-        return fail(DICE_E_ARG, "NULL file arrays");
+    if (f->n_files > 0 && check_files(f)) return DICE_E_ARG;
     DeviceGuard g(c->device);
-    hipStream_t s = pick_stream(c, stream);
+    hipStream_t s = stream_of(c, stream);
     const int64_t n = f->n_files;
-    b->n = n;
-    b->n_long = 0;
-    b->fmask_device = false;
-    b->text_state = 0;
-    ++b->epoch;
-    b->text_utf8 = false;
+    begin_upload(b, n);
     if (n == 0) return DICE_OK;
     HIP_TRY(hipMemcpyAsync(b->d_rows, f->bits, (size_t)n * c->w64 * 8, hipMemcpyHostToDevice, s));
     return dice::upload_tail(b, n, f->wordset_size, f->length, f->cc_false_positive, s);
@@ -605,12 +545,7 @@ int dice_batch_upload(dice_batch* b, const dice_files* f, void* stream) {
 int dice::upload_rows_resident(dice_batch* b, const dice_files* f, hipStream_t s) {
     if (f->n_files < 0 || f->n_files > b->capacity) return fail(DICE_E_ARG, "n_files exceeds batch capacity");
     DeviceGuard g(b->ctx->device);
-    b->n = f->n_files;
-    b->n_long = 0;
-    b->fmask_device = false;
-    b->text_state = 0;
-    ++b->epoch;
-    b->text_utf8 = false;
+    begin_upload(b, f->n_files);
     if (b->n == 0) return DICE_OK;
     return upload_tail(b, b->n, f->wordset_size, f->length, f->cc_false_positive, s);
 }
@@ -632,28 +567,13 @@ int dice_batch_upload_ids(dice_batch* b, int64_t n, const int64_t* offsets, cons
     }
     if ((int64_t)c->w64 * 8 * 4 > 64 * 1024) return fail(DICE_E_ARG, "vocabulary too large for id upload");
     DeviceGuard g(c->device);
-    hipStream_t s = pick_stream(c, stream);
-    b->n = n;
-    b->n_long = 0;
-    b->fmask_device = false;
-    b->text_state = 0;
-    ++b->epoch;
-    b->text_utf8 = false;
+    hipStream_t s = stream_of(c, stream);
+    begin_upload(b, n);
     if (n == 0) return DICE_OK;
-    const size_t need = (size_t)std::max<int64_t>(offsets[n], 1) * (size_t)id_bytes;
-    if (need > b->ids_bytes) {
-        HIP_TRY(hipStreamSynchronize(s));   // the staging may still feed an earlier upload
-        if (b->d_ids) (void)hipFree(b->d_ids);
-        b->d_ids = nullptr;
-        b->ids_bytes = 0;
-        int rc = dalloc_bytes(&b->d_ids, need);
-        if (rc) return rc;
-        b->ids_bytes = need;
-    }
-    if (!b->d_offs) {
-        int rc = dalloc_bytes(reinterpret_cast<void**>(&b->d_offs), (size_t)(b->capacity + 1) * 8);
-        if (rc) return rc;
-    }
+    int rc;   // (the id staging may still feed an earlier upload: wait for the stream before it is freed)
+    if ((rc = b->d_ids.reserve((size_t)std::max<int64_t>(offsets[n], 1) * (size_t)id_bytes, s)) ||
+        (rc = b->d_offs.reserve((size_t)b->capacity + 1)))
+        return rc;
     HIP_TRY(hipMemcpyAsync(b->d_offs, offsets, (size_t)(n + 1) * 8, hipMemcpyHostToDevice, s));
     if (offsets[n] > 0)
         HIP_TRY(hipMemcpyAsync(b->d_ids, ids, (size_t)offsets[n] * (size_t)id_bytes, hipMemcpyHostToDevice, s));
@@ -661,10 +581,10 @@ int dice_batch_upload_ids(dice_batch* b, int64_t n, const int64_t* offsets, cons
     const size_t lds = (size_t)4 * c->w64 * 8;
     if (id_bytes == 2)
         hipLaunchKernelGGL(dice_rows_from_ids<uint16_t>, dim3(grid), dim3(256), lds, s, b->d_offs,
-                           (const uint16_t*)b->d_ids, n, c->w64, (uint32_t)c->V, b->d_rows);
+                           (const uint16_t*)b->d_ids.get(), n, c->w64, (uint32_t)c->V, b->d_rows);
     else
         hipLaunchKernelGGL(dice_rows_from_ids<uint32_t>, dim3(grid), dim3(256), lds, s, b->d_offs,
-                           (const uint32_t*)b->d_ids, n, c->w64, (uint32_t)c->V, b->d_rows);
+                           (const uint32_t*)b->d_ids.get(), n, c->w64, (uint32_t)c->V, b->d_rows);
     HIP_TRY(hipGetLastError());
     return dice::upload_tail(b, n, wordset_size, length, cc, s);
 }
@@ -692,7 +612,7 @@ static int batch_match(dice_batch* b, double thr, void* stream, bool confidence)
         return DICE_OK;
     }
     DeviceGuard g(c->device);
-    hipStream_t s = pick_stream(c, stream);
+    hipStream_t s = stream_of(c, stream);
     const int64_t n_tiles = (b->n + kWave - 1) / kWave;
     const unsigned grid = (unsigned)((n_tiles + (kBlock / kWave) - 1) / (kBlock / kWave));
     if (c->kind == 1) {
@@ -734,18 +654,9 @@ int dice_batch_match_confidence(dice_batch* b, double thr, void* stream) { retur
 
 // The [n][k] ranking buffers, all dice_batch_topk allocates.
 static int ensure_topk(dice_batch* b, int32_t k) {
-    if (b->tk_cap >= b->capacity && b->mat_k >= k && b->d_tki) return DICE_OK;
-    if (b->d_tki) (void)hipFree(b->d_tki);
-    if (b->d_tks) (void)hipFree(b->d_tks);
-    b->d_tki = nullptr; b->d_tks = nullptr;
-    b->tk_cap = 0;
-    int rc;
-    const int32_t kk = std::max<int32_t>(k, 1);
-    if ((rc = dalloc(&b->d_tki, (size_t)b->capacity * kk)) || (rc = dalloc(&b->d_tks, (size_t)b->capacity * kk)))
-        return rc;
-    b->tk_cap = b->capacity;
-    b->mat_k = kk;
-    return DICE_OK;
+    const size_t need = (size_t)b->capacity * std::max<int32_t>(k, 1);
+    int rc = b->d_tki.reserve(need);
+    return rc ? rc : b->d_tks.reserve(need);
 }
 
 static int ensure_matrix(dice_batch* b, int32_t k) {
@@ -754,21 +665,26 @@ static int ensure_matrix(dice_batch* b, int32_t k) {
     if (rc) return rc;
     // row stride: kind 3 writes [n][post_ld] rows of whole 128-byte lines, the others [T][n]
     b->mat_ld = c->kind == 3 ? c->post_ld : c->T;
-    if (b->mat_cap >= b->capacity && b->d_mov) return DICE_OK;
-    if (b->d_mov) (void)hipFree(b->d_mov);
-    if (b->d_mscore) (void)hipFree(b->d_mscore);
-    b->d_mov = nullptr; b->d_mscore = nullptr;
-    b->mat_cap = 0;
-    if ((rc = dalloc(&b->d_mov, (size_t)b->capacity * b->mat_ld)) ||
-        (rc = dalloc(&b->d_mscore, (size_t)b->capacity * b->mat_ld)))
-        return rc;
-    b->mat_cap = b->capacity;
-    return DICE_OK;
+    const size_t need = (size_t)b->capacity * b->mat_ld;
+    rc = b->d_mov.reserve(need);
+    return rc ? rc : b->d_mscore.reserve(need);
 }
 
 int64_t dice_batch_matrix_bytes(const dice_batch* b) {
     if (!b) return -1;
-    return b->d_mov && b->d_mscore ? b->mat_cap * (int64_t)b->mat_ld * 12 : 0;
+    return b->d_mov && b->d_mscore ? b->capacity * (int64_t)b->mat_ld * 12 : 0;
+}
+
+// The dense kernel's ranking (kinds 0 and 2), with the N x T rows when `mov` and `mscore` are given
+// (the reference and fallback kernel skips the rows of NULL matrix pointers).
+static int launch_dense_matrix(dice_batch* b, int32_t k, uint32_t* mov, double* mscore, hipStream_t s) {
+    dice_ctx* c = b->ctx;
+    const int64_t n_tiles = (b->n + kWave - 1) / kWave;
+    const unsigned grid = (unsigned)((n_tiles + (kBlock / kWave) - 1) / (kBlock / kWave));
+    auto kern = k <= 4 ? dice_dense_matrix<kTT, 4> : dice_dense_matrix<kTT, kTopKMax>;
+    hipLaunchKernelGGL(kern, dim3(grid), dim3(kBlock), 0, s, b->d_tiles, b->n, c->wq, c->d_tq, c->d_tc, c->T, c->tpad,
+                       b->d_wf, b->d_len, b->d_cc, k, mov, mscore, k > 0 ? b->d_tki.get() : nullptr, b->d_tks);
+    return DICE_OK;
 }
 
 int dice_batch_matrix(dice_batch* b, int32_t k, void* stream) {
@@ -781,26 +697,12 @@ int dice_batch_matrix(dice_batch* b, int32_t k, void* stream) {
     DeviceGuard g(c->device);
     int rc = ensure_matrix(b, k);
     if (rc) return rc;
-    hipStream_t s = pick_stream(c, stream);
-    const int64_t n_tiles = (b->n + kWave - 1) / kWave;
-    const unsigned grid = (unsigned)((n_tiles + (kBlock / kWave) - 1) / (kBlock / kWave));
+    hipStream_t s = stream_of(c, stream);
     b->mat_rowmajor = c->kind == 3;
-    if (c->kind == 1) {
-        rc = dice::program_launch_matrix(c, b, k, s);
-        if (rc != DICE_OK) return rc;
-    } else if (c->kind == 3) {
-        rc = dice::post_launch_matrix(c, b, k, s);
-        if (rc != DICE_OK) return rc;
-    } else {
-        if (k <= 4)
-            hipLaunchKernelGGL((dice_dense_matrix<kTT, 4>), dim3(grid), dim3(kBlock), 0, s, b->d_tiles, b->n,
-                               c->wq, c->d_tq, c->d_tc, c->T, c->tpad, b->d_wf, b->d_len, b->d_cc, k, b->d_mov,
-                               b->d_mscore, k > 0 ? b->d_tki : nullptr, b->d_tks);
-        else
-            hipLaunchKernelGGL((dice_dense_matrix<kTT, kTopKMax>), dim3(grid), dim3(kBlock), 0, s, b->d_tiles,
-                               b->n, c->wq, c->d_tq, c->d_tc, c->T, c->tpad, b->d_wf, b->d_len, b->d_cc, k,
-                               b->d_mov, b->d_mscore, k > 0 ? b->d_tki : nullptr, b->d_tks);
-    }
+    rc = c->kind == 1   ? dice::program_launch_matrix(c, b, k, s)
+         : c->kind == 3 ? dice::post_launch_matrix(c, b, k, s)
+                        : launch_dense_matrix(b, k, b->d_mov, b->d_mscore, s);
+    if (rc != DICE_OK) return rc;
     HIP_TRY(hipGetLastError());
     return DICE_OK;
 }
@@ -817,29 +719,12 @@ int dice_batch_topk(dice_batch* b, int32_t k, void* stream) {
     DeviceGuard g(c->device);
     int rc = ensure_topk(b, k);
     if (rc) return rc;
-    hipStream_t s = pick_stream(c, stream);
+    hipStream_t s = stream_of(c, stream);
     b->mat_rowmajor = c->kind == 3;
-    if (c->kind == 1) {
-        rc = dice::program_launch_topk(c, b, k, s);
-        if (rc != DICE_OK) return rc;
-    } else if (c->kind == 3) {
-        rc = dice::post_launch_topk(c, b, k, s);
-        if (rc != DICE_OK) return rc;
-    } else {
-        // the reference and fallback kernel skips the rows of NULL matrix pointers
-        const int64_t n_tiles = (b->n + kWave - 1) / kWave;
-        const unsigned grid = (unsigned)((n_tiles + (kBlock / kWave) - 1) / (kBlock / kWave));
-        uint32_t* no_ov = nullptr;
-        double* no_score = nullptr;
-        if (k <= 4)
-            hipLaunchKernelGGL((dice_dense_matrix<kTT, 4>), dim3(grid), dim3(kBlock), 0, s, b->d_tiles, b->n,
-                               c->wq, c->d_tq, c->d_tc, c->T, c->tpad, b->d_wf, b->d_len, b->d_cc, k, no_ov, no_score,
-                               b->d_tki, b->d_tks);
-        else
-            hipLaunchKernelGGL((dice_dense_matrix<kTT, kTopKMax>), dim3(grid), dim3(kBlock), 0, s, b->d_tiles,
-                               b->n, c->wq, c->d_tq, c->d_tc, c->T, c->tpad, b->d_wf, b->d_len, b->d_cc, k, no_ov,
-                               no_score, b->d_tki, b->d_tks);
-    }
+    rc = c->kind == 1   ? dice::program_launch_topk(c, b, k, s)
+         : c->kind == 3 ? dice::post_launch_topk(c, b, k, s)
+                        : launch_dense_matrix(b, k, nullptr, nullptr, s);
+    if (rc != DICE_OK) return rc;
     HIP_TRY(hipGetLastError());
     return DICE_OK;
 }
@@ -908,7 +793,7 @@ int dice_batch_download_match(dice_batch* b, int32_t* best, uint32_t* ov, double
     if (!b) return fail(DICE_E_ARG, "NULL batch");
     dice_ctx* c = b->ctx;
     DeviceGuard g(c->device);
-    return dice::download_match_to(b, best, ov, score, pick_stream(c, stream), hipMemcpyDeviceToHost);
+    return dice::download_match_to(b, best, ov, score, stream_of(c, stream), hipMemcpyDeviceToHost);
 }
 
 int dice_batch_download_matrix(dice_batch* b, uint32_t* ov, double* score, int32_t k, int32_t* tki, double* tks,
@@ -921,7 +806,7 @@ int dice_batch_download_matrix(dice_batch* b, uint32_t* ov, double* score, int32
         return fail(DICE_E_STATE, "the last ranking was dice_batch_topk: no N x T matrix on the device");
     dice_ctx* c = b->ctx;
     DeviceGuard g(c->device);
-    return dice::download_matrix_to(b, ov, score, tki, tks, pick_stream(c, stream), hipMemcpyDeviceToHost);
+    return dice::download_matrix_to(b, ov, score, tki, tks, stream_of(c, stream), hipMemcpyDeviceToHost);
 }
 
 int dice_batch_download_topk(dice_batch* b, int32_t k, int32_t* tki, double* tks, void* stream) {
@@ -933,7 +818,7 @@ int dice_batch_download_topk(dice_batch* b, int32_t k, int32_t* tki, double* tks
                                     std::to_string(b->k_used) + ")");
     dice_ctx* c = b->ctx;
     DeviceGuard g(c->device);
-    return dice::download_topk_to(b, tki, tks, pick_stream(c, stream), hipMemcpyDeviceToHost);
+    return dice::download_topk_to(b, tki, tks, stream_of(c, stream), hipMemcpyDeviceToHost);
 }
 
 int dice_batch_stream_probe(dice_batch* b, void* stream) {
@@ -942,12 +827,12 @@ int dice_batch_stream_probe(dice_batch* b, void* stream) {
     if (b->n == 0) return DICE_OK;
     if (c->w64 < 2) return fail(DICE_E_STATE, "probe needs >= 2 words per file");
     DeviceGuard g(c->device);
-    hipStream_t s = pick_stream(c, stream);
+    hipStream_t s = stream_of(c, stream);
     const int64_t n_tiles = (b->n + kWave - 1) / kWave;
     const unsigned grid = (unsigned)((n_tiles + (kBlock / kWave) - 1) / (kBlock / kWave));
     // results land in the (16 B/file) score+best+overlap area: reuse d_score as scratch
     hipLaunchKernelGGL(dice_stream_probe, dim3(grid), dim3(kBlock), 0, s, b->d_tiles, b->n, c->twq,
-                       reinterpret_cast<uint4*>(b->d_rows));
+                       reinterpret_cast<uint4*>(b->d_rows.get()));
     HIP_TRY(hipGetLastError());
     return DICE_OK;
 }
@@ -960,7 +845,7 @@ int dice_batch_deferred(dice_batch* b, int64_t* deferred, void* stream) {
     if (!b->d_ndefer || !b->ctx->prune || b->last_match != 2) return DICE_OK;
     DeviceGuard g(b->ctx->device);
     uint32_t m = 0;
-    hipStream_t s = pick_stream(b->ctx, stream);
+    hipStream_t s = stream_of(b->ctx, stream);
     HIP_TRY(hipMemcpyAsync(&m, b->d_ndefer, 4, hipMemcpyDeviceToHost, s));
     HIP_TRY(hipStreamSynchronize(s));
     *deferred = m;
@@ -977,7 +862,7 @@ int dice_batch_scored_pairs(dice_batch* b, int64_t* pairs, void* stream) {
         // the pruned kernel's exact scores (per-wave counts) + every pair of each deferred file
         // (the postings kernels score them all)
         DeviceGuard g(c->device);
-        hipStream_t s = pick_stream(c, stream);
+        hipStream_t s = stream_of(c, stream);
         // (dice_prune4's per-wave counts, then the number of files the postings kernels scored)
         const int64_t nw = b->prune_waves;
         std::vector<uint32_t> h((size_t)nw + 1);
@@ -1052,41 +937,42 @@ SmallLayout small_layout(const dice_ctx* c) {
     return L;
 }
 
+// buf = `count` elements of `region` from byte `offset` on
+template <class T>
+void window(DevBuf<T>& buf, const DevBytes& region, size_t offset, size_t count) {
+    buf.view(reinterpret_cast<T*>(region.get() + offset), count);
+}
+
+// The small-call batch: inputs and results are windows into d_in and d_out. The ranking windows hold
+// kSmallFiles files, so dice_batch_matrix / dice_batch_topk never allocate here; small_matrix and
+// small_topk move them (packed for the call's n) before every call.
 int small_batch(dice_ctx* c, dice_batch** out) {
     if (c->small) {
         *out = c->small;
         return DICE_OK;
     }
     const SmallLayout L = small_layout(c);
+    const size_t n = (size_t)kSmallFiles, T = (size_t)std::max(c->T, c->post_ld), K = (size_t)DICE_TOPK_MAX;
     dice_batch* b = nullptr;
-    int rc = dice_batch_create(c, kSmallFiles, &b);
+    int rc = batch_new(c, kSmallFiles, &b);
     if (rc) return rc;
-    void* old[] = {b->d_rows, b->d_wf, b->d_len, b->d_cc, b->d_best, b->d_ov, b->d_score};
-    for (void* p : old) (void)hipFree(p);
-    b->d_rows = nullptr; b->d_wf = nullptr; b->d_len = nullptr; b->d_cc = nullptr;
-    b->d_best = nullptr; b->d_ov = nullptr; b->d_score = nullptr;
-    if ((rc = dice::dalloc_bytes(&b->d_in, L.in_bytes)) || (rc = dice::dalloc_bytes(&b->d_out, L.out_bytes)) ||
+    if ((rc = b->d_in.reserve(L.in_bytes)) || (rc = b->d_out.reserve(L.out_bytes)) ||
         (!c->h_small_in && hipHostMalloc(&c->h_small_in, L.in_bytes, hipHostMallocDefault) != hipSuccess) ||
         (!c->h_small_out && hipHostMalloc(&c->h_small_out, L.out_bytes, hipHostMallocDefault) != hipSuccess)) {
-        dice_batch_destroy(b);
+        delete b;
         return rc ? rc : fail(DICE_E_NOMEM, "hipHostMalloc failed");
     }
-    char* in = (char*)b->d_in;
-    char* o = (char*)b->d_out;
-    b->d_wf = (uint32_t*)(in + L.wf);
-    b->d_len = (int32_t*)(in + L.len);
-    b->d_cc = (uint8_t*)(in + L.cc);
-    b->d_rows = (uint64_t*)(in + L.rows);
-    b->d_best = (int32_t*)(o + L.best);
-    b->d_ov = (uint32_t*)(o + L.ov);
-    b->d_score = (double*)(o + L.score);
-    b->d_mov = (uint32_t*)(o + L.mov);
-    b->d_mscore = (double*)(o + L.mscore);
-    b->d_tki = (int32_t*)(o + L.tki);
-    b->d_tks = (double*)(o + L.tks);
-    b->mat_cap = kSmallFiles;
-    b->tk_cap = kSmallFiles;
-    b->mat_k = DICE_TOPK_MAX;
+    window(b->d_wf, b->d_in, L.wf, n);
+    window(b->d_len, b->d_in, L.len, n);
+    window(b->d_cc, b->d_in, L.cc, n);
+    window(b->d_rows, b->d_in, L.rows, n * c->w64);
+    window(b->d_best, b->d_out, L.best, n);
+    window(b->d_ov, b->d_out, L.ov, n);
+    window(b->d_score, b->d_out, L.score, n);
+    window(b->d_mov, b->d_out, L.mov, n * T);
+    window(b->d_mscore, b->d_out, L.mscore, n * T);
+    window(b->d_tki, b->d_out, L.tki, n * K);
+    window(b->d_tks, b->d_out, L.tks, n * K);
     c->small = b;
     *out = b;
     return DICE_OK;
@@ -1107,9 +993,7 @@ int small_upload(dice_ctx* c, dice_batch* b, const dice_files* f, const SmallLay
     b->n = n;
     HIP_TRY(hipMemcpyAsync(b->d_in, h, L.rows + (size_t)n * c->w64 * 8, hipMemcpyHostToDevice, c->stream));
     if (c->kind == 3) {   // (dice_match's long-file routing, upload_tail)
-        b->n_long = 0;
-        if (c->prune)
-            for (int64_t i = 0; i < n; ++i) b->n_long += f->wordset_size[i] > c->prune_max_lf;
+        b->n_long = count_long(c, f->wordset_size, n);
         return DICE_OK;
     }
     return launch_pack(c, b, n, c->stream);
@@ -1146,11 +1030,14 @@ int small_matrix(dice_ctx* c, const dice_files* f, uint32_t* ov, double* score, 
     const size_t ld = c->kind == 3 ? (size_t)c->post_ld : T;   // row-major rows at stride ld (kind 3)
     const size_t o_mov = L.mov, o_msc = align_up(o_mov + n * ld * 4), o_tki = align_up(o_msc + n * ld * 8),
                  o_tks = align_up(o_tki + n * kk * 4), o_end = o_tks + n * kk * 8;
-    char* d = (char*)b->d_out;
-    b->d_mov = (uint32_t*)(d + o_mov);
-    b->d_mscore = (double*)(d + o_msc);
-    b->d_tki = (int32_t*)(d + o_tki);
-    b->d_tks = (double*)(d + o_tks);
+    char* d = (char*)b->d_out.get();
+    // (the counts are the full-capacity figures that reserve() in dice_batch_matrix compares against, not
+    // the packed n * ld and n * k this call writes: as full-size windows they overlap one another, and
+    // each still ends inside d_out, since every packed offset is at most its small_layout offset)
+    window(b->d_mov, b->d_out, o_mov, kSmallFiles * ld);
+    window(b->d_mscore, b->d_out, o_msc, kSmallFiles * ld);
+    window(b->d_tki, b->d_out, o_tki, kSmallFiles * (size_t)DICE_TOPK_MAX);
+    window(b->d_tks, b->d_out, o_tks, kSmallFiles * (size_t)DICE_TOPK_MAX);
     if ((rc = small_upload(c, b, f, L)) || (rc = dice_batch_matrix(b, k, nullptr))) return rc;
     HIP_TRY(hipMemcpyAsync((char*)c->h_small_out + o_mov, d + o_mov, o_end - o_mov, hipMemcpyDeviceToHost,
                            c->stream));
@@ -1193,9 +1080,10 @@ int small_topk(dice_ctx* c, const dice_files* f, int32_t k, int32_t* tki, double
     const SmallLayout L = small_layout(c);
     const size_t n = (size_t)f->n_files, kk = (size_t)k;
     const size_t o_tki = L.tki, o_tks = align_up(o_tki + n * kk * 4), o_end = o_tks + n * kk * 8;
-    char* d = (char*)b->d_out;
-    b->d_tki = (int32_t*)(d + o_tki);
-    b->d_tks = (double*)(d + o_tks);
+    char* d = (char*)b->d_out.get();
+    // (counts: dice_batch_topk's reserve figure, as in small_matrix; the call writes n * k entries)
+    window(b->d_tki, b->d_out, o_tki, kSmallFiles * (size_t)DICE_TOPK_MAX);
+    window(b->d_tks, b->d_out, o_tks, kSmallFiles * (size_t)DICE_TOPK_MAX);
     if ((rc = small_upload(c, b, f, L)) || (rc = dice_batch_topk(b, k, nullptr))) return rc;
     HIP_TRY(hipMemcpyAsync((char*)c->h_small_out + o_tki, d + o_tki, o_end - o_tki, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
@@ -1223,8 +1111,7 @@ static int host_match(dice_ctx* ctx, const dice_files* f, double thr, int32_t* b
     if (!ctx || !f) return fail(DICE_E_ARG, "NULL ctx/files");
     if (f->n_files == 0) return DICE_OK;
     if (f->n_files < 0) return fail(DICE_E_ARG, "n_files < 0");
-    if (!f->bits || !f->wordset_size || !f->length || !f->cc_false_positive)
-        return fail(DICE_E_ARG, "NULL file arrays");
+    if (check_files(f)) return DICE_E_ARG;
     if (f->n_files <= kSmallFiles && !getenv_flag("DICE_NO_SMALL_CALL"))
         return small_match(ctx, f, thr, best, ov, score, confidence);
     dice_batch* b = nullptr;
@@ -1250,8 +1137,7 @@ int dice_similarity_matrix(dice_ctx* ctx, const dice_files* f, uint32_t* ov, dou
     if (k > 0 && (!tki || !tks)) return fail(DICE_E_ARG, "top-k outputs required when k > 0");
     if (f->n_files == 0) return DICE_OK;
     if (f->n_files < 0) return fail(DICE_E_ARG, "n_files < 0");
-    if (!f->bits || !f->wordset_size || !f->length || !f->cc_false_positive)
-        return fail(DICE_E_ARG, "NULL file arrays");
+    if (check_files(f)) return DICE_E_ARG;
     if (f->n_files <= kSmallFiles && !getenv_flag("DICE_NO_SMALL_CALL")) return small_matrix(ctx, f, ov, score, k, tki, tks);
     dice_batch* b = nullptr;
     int rc = dice::scratch_for(ctx, f->n_files, &b);
@@ -1267,8 +1153,7 @@ int dice_topk(dice_ctx* ctx, const dice_files* f, int32_t k, int32_t* tki, doubl
     if (!tki || !tks) return fail(DICE_E_ARG, "top-k outputs required");
     if (f->n_files == 0) return DICE_OK;
     if (f->n_files < 0) return fail(DICE_E_ARG, "n_files < 0");
-    if (!f->bits || !f->wordset_size || !f->length || !f->cc_false_positive)
-        return fail(DICE_E_ARG, "NULL file arrays");
+    if (check_files(f)) return DICE_E_ARG;
     if (f->n_files <= kSmallFiles && !getenv_flag("DICE_NO_SMALL_CALL")) return small_topk(ctx, f, k, tki, tks);
     dice_batch* b = nullptr;
     int rc = dice::scratch_for(ctx, f->n_files, &b);

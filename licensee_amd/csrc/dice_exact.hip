@@ -90,27 +90,7 @@ __global__ __launch_bounds__(256) void dice_exact_kernel(const uint64_t* __restr
     if (valid) out[f] = res;
 }
 
-struct Guard {
-    int prev = -1;
-    explicit Guard(int dev) {
-        if (hipGetDevice(&prev) != hipSuccess) prev = -1;
-        (void)hipSetDevice(dev);
-    }
-    ~Guard() {
-        if (prev >= 0) (void)hipSetDevice(prev);
-    }
-};
-
-hipStream_t stream_of(dice_ctx* c, void* s) { return s ? (hipStream_t)s : c->stream; }
-
 }  // namespace
-
-void exact_free(dice_ctx* c) {
-    for (void* p : {c->d_ex_tbl, c->d_ex_need, c->d_ex_rec})
-        if (p) (void)hipFree(p);
-    c->d_ex_tbl = c->d_ex_need = c->d_ex_rec = nullptr;
-    c->exact_ready = false;
-}
 
 }  // namespace dice
 
@@ -142,12 +122,12 @@ int dice_exact_setup(dice_ctx* c, const uint32_t* wordset_size, const uint64_t* 
         need[(size_t)k] = field_need ? field_need[t] : 0ull;
     }
     if (rec.empty()) rec.push_back(make_uint4(0, 0, 0, 0));
-    dice::Guard g(c->device);
-    dice::exact_free(c);
+    dice::DeviceGuard g(c->device);
+    c->exact_ready = false;   // the old tables go whether or not the new ones arrive
+    c->d_ex_tbl.reset(), c->d_ex_need.reset(), c->d_ex_rec.reset();
     int rc;
-    if ((rc = dice::dalloc_bytes(&c->d_ex_tbl, tbl.size() * 16)) ||
-        (rc = dice::dalloc_bytes(&c->d_ex_need, need.size() * 8)) ||
-        (rc = dice::dalloc_bytes(&c->d_ex_rec, rec.size() * 16)))
+    if ((rc = c->d_ex_tbl.reserve(tbl.size() * 16)) || (rc = c->d_ex_need.reserve(need.size() * 8)) ||
+        (rc = c->d_ex_rec.reserve(rec.size() * 16)))
         return rc;
     if (hipMemcpy(c->d_ex_tbl, tbl.data(), tbl.size() * 16, hipMemcpyHostToDevice) != hipSuccess ||
         hipMemcpy(c->d_ex_need, need.data(), need.size() * 8, hipMemcpyHostToDevice) != hipSuccess ||
@@ -161,10 +141,9 @@ int dice_batch_exact(dice_batch* b, const uint64_t* file_field_mask, void* strea
     if (!b) return fail(DICE_E_ARG, "NULL batch");
     dice_ctx* c = b->ctx;
     if (!c->exact_ready) return fail(DICE_E_STATE, "dice_exact_setup was not called");
-    dice::Guard g(c->device);
+    dice::DeviceGuard g(c->device);
     int rc;
-    if (!b->d_exact && (rc = dice::dalloc_bytes((void**)&b->d_exact, (size_t)b->capacity * 4))) return rc;
-    if (!b->d_fmask && (rc = dice::dalloc_bytes((void**)&b->d_fmask, (size_t)b->capacity * 8))) return rc;
+    if ((rc = b->d_exact.reserve((size_t)b->capacity)) || (rc = b->d_fmask.reserve((size_t)b->capacity))) return rc;
     b->exact_epoch = b->epoch;
     if (b->n == 0) return DICE_OK;
     b->exact_epoch = 0;
@@ -177,8 +156,8 @@ int dice_batch_exact(dice_batch* b, const uint64_t* file_field_mask, void* strea
     const unsigned grid = (unsigned)((b->n + 255) / 256);
     hipLaunchKernelGGL(dice::dice_exact_kernel, dim3(grid), dim3(256), (size_t)c->T * 4, s,
                        (const uint64_t*)b->d_rows, b->n, c->w64, (const uint32_t*)b->d_wf,
-                       masks ? (const uint64_t*)b->d_fmask : nullptr, (const uint4*)c->d_ex_tbl,
-                       (const uint64_t*)c->d_ex_need, (const uint4*)c->d_ex_rec, c->T, b->d_exact);
+                       masks ? b->d_fmask.get() : nullptr, (const uint4*)c->d_ex_tbl.get(),
+                       (const uint64_t*)c->d_ex_need.get(), (const uint4*)c->d_ex_rec.get(), c->T, b->d_exact);
     if (hipGetLastError() != hipSuccess) return fail(DICE_E_DEVICE, "dice_exact_kernel launch failed");
     b->exact_epoch = b->epoch;
     return DICE_OK;
@@ -187,7 +166,7 @@ int dice_batch_exact(dice_batch* b, const uint64_t* file_field_mask, void* strea
 int dice_batch_download_exact(dice_batch* b, int32_t* exact, void* stream) {
     if (!b || !exact) return fail(DICE_E_ARG, "NULL batch/output");
     if (b->n && !b->d_exact) return fail(DICE_E_STATE, "dice_batch_exact was not run");
-    dice::Guard g(b->ctx->device);
+    dice::DeviceGuard g(b->ctx->device);
     hipStream_t s = dice::stream_of(b->ctx, stream);
     if (b->n && hipMemcpyAsync(exact, b->d_exact, (size_t)b->n * 4, hipMemcpyDeviceToHost, s) != hipSuccess)
         return fail(DICE_E_DEVICE, "exact download failed");

@@ -151,20 +151,6 @@ __global__ __launch_bounds__(kWave) void dice_sha1_kernel(const uint8_t* __restr
     }
 }
 
-namespace {
-
-struct HGuard {
-    int prev = -1;
-    explicit HGuard(int dev) {
-        if (hipGetDevice(&prev) != hipSuccess) prev = -1;
-        (void)hipSetDevice(dev);
-    }
-    ~HGuard() {
-        if (prev >= 0) (void)hipSetDevice(prev);
-    }
-};
-
-}  // namespace
 }  // namespace dice
 
 using dice::fail;
@@ -181,19 +167,19 @@ int dice_batch_content_hash(dice_batch* b, void* stream) {
         b->text_state = 2;
         return DICE_OK;
     }
-    dice::HGuard g(c->device);
-    hipStream_t s = stream ? (hipStream_t)stream : c->stream;
+    dice::DeviceGuard g(c->device);
+    hipStream_t s = dice::stream_of(c, stream);
     int rc;
     // digests [capacity][20] (read as 5 words each), status [capacity], the file counter
-    if (!b->d_hdig && (rc = dice::dalloc_bytes(reinterpret_cast<void**>(&b->d_hdig), (size_t)b->capacity * 20))) return rc;
-    if (!b->d_hstat && (rc = dice::dalloc_bytes(reinterpret_cast<void**>(&b->d_hstat), (size_t)b->capacity))) return rc;
-    if (!b->d_hcnt && (rc = dice::dalloc_bytes(reinterpret_cast<void**>(&b->d_hcnt), 4))) return rc;
+    if ((rc = b->d_hdig.reserve((size_t)b->capacity * 20)) || (rc = b->d_hstat.reserve((size_t)b->capacity)) ||
+        (rc = b->d_hcnt.reserve(1)))
+        return rc;
     if (hipMemsetAsync(b->d_hcnt, 0, 4, s) != hipSuccess) return fail(DICE_E_DEVICE, "hipMemsetAsync failed");
     // one lane per file; at most 16 waves per SIMD's worth of lanes, the rest of the files are
     // taken from the counter
     const int64_t waves = std::min<int64_t>((n + dice::kWave - 1) / dice::kWave, (int64_t)c->n_cu * 16);
     hipLaunchKernelGGL(dice::dice_sha1_kernel, dim3((unsigned)waves), dim3(dice::kWave), 0, s, (const uint8_t*)b->d_text,
-                       (const int64_t*)b->d_toff, (const int32_t*)b->d_tlen, n, b->d_hcnt, (uint32_t*)b->d_hdig, b->d_hstat,
+                       (const int64_t*)b->d_toff, (const int32_t*)b->d_tlen, n, b->d_hcnt, (uint32_t*)b->d_hdig.get(), b->d_hstat,
                        b->text_utf8 ? 0u : 0x80808080u);
     if (hipGetLastError() != hipSuccess) return fail(DICE_E_DEVICE, "dice_sha1_kernel launch failed");
     b->text_state = 2;
@@ -204,8 +190,8 @@ int dice_batch_download_content_hash(dice_batch* b, uint8_t* digest, uint8_t* st
     if (!b) return fail(DICE_E_ARG, "NULL batch");
     dice_ctx* c = b->ctx;
     if (b->text_state != 2) return fail(DICE_E_STATE, "no content hash was computed since the last upload");
-    dice::HGuard g(c->device);
-    hipStream_t s = stream ? (hipStream_t)stream : c->stream;
+    dice::DeviceGuard g(c->device);
+    hipStream_t s = dice::stream_of(c, stream);
     const size_t n = (size_t)b->n;
     if (n && ((digest && hipMemcpyAsync(digest, b->d_hdig, n * 20, hipMemcpyDeviceToHost, s) != hipSuccess) ||
               (status && hipMemcpyAsync(status, b->d_hstat, n, hipMemcpyDeviceToHost, s) != hipSuccess)))

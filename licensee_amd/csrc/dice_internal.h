@@ -7,6 +7,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <string>
+#include <utility>
 #include <vector>
 
 #include "../../include/licensee_dice.h"
@@ -43,13 +44,76 @@ inline const char* diag_env(const char* name) {
 #endif
 }
 
-inline int dalloc_bytes(void** p, size_t bytes) {
-    if (hipMalloc(p, bytes ? bytes : 1) != hipSuccess) {
-        *p = nullptr;
-        return fail(DICE_E_NOMEM, "hipMalloc failed");
+// ---- device plumbing: the one set-device guard, the one HIP check, the one owner of device memory ----
+
+struct DeviceGuard {
+    int prev = -1;
+    bool ok = false;
+    explicit DeviceGuard(int dev) {
+        if (hipGetDevice(&prev) != hipSuccess) prev = -1;
+        ok = hipSetDevice(dev) == hipSuccess;
     }
-    return DICE_OK;
-}
+    ~DeviceGuard() {
+        if (prev >= 0) (void)hipSetDevice(prev);
+    }
+};
+
+#define HIP_TRY(expr)                                                                                  \
+    do {                                                                                               \
+        hipError_t e_ = (expr);                                                                        \
+        if (e_ != hipSuccess)                                                                          \
+            return ::dice::fail(DICE_E_DEVICE, std::string(#expr) + ": " + hipGetErrorString(e_));     \
+    } while (0)
+
+// Move-only owner of one device allocation of `count` elements (a byte buffer, DevBytes, where the
+// element type lives in another file), or a non-owning window into another buffer (view).
+// reserve(count) frees without waiting and reserve(count, stream) waits for `stream` first: the second
+// form stands where the code always waited for the stream that may still read the buffer; whether the
+// others need a wait is unknown -- they lean on hipFree, which waits for the device's work itself.
+template <class T>
+class DevBuf {
+    T* p_ = nullptr;
+    size_t cap_ = 0;
+    bool owned_ = true;
+
+public:
+    DevBuf() = default;
+    DevBuf(DevBuf&& o) noexcept : p_(o.p_), cap_(o.cap_), owned_(o.owned_) { o.p_ = nullptr, o.cap_ = 0; }
+    DevBuf& operator=(DevBuf&& o) noexcept {   // (what this held goes with `o`)
+        std::swap(p_, o.p_), std::swap(cap_, o.cap_), std::swap(owned_, o.owned_);
+        return *this;
+    }
+    ~DevBuf() { reset(); }
+    void reset() {
+        if (p_ && owned_) (void)hipFree(p_);
+        p_ = nullptr, cap_ = 0, owned_ = true;
+    }
+    // no-op while the capacity suffices; a count of 0 allocates one element
+    int reserve(size_t count) {
+        if (p_ && cap_ >= count) return DICE_OK;
+        reset();
+        if (hipMalloc(reinterpret_cast<void**>(&p_), (count ? count : 1) * sizeof(T)) != hipSuccess) {
+            p_ = nullptr;
+            return fail(DICE_E_NOMEM, "hipMalloc failed");
+        }
+        cap_ = count;
+        return DICE_OK;
+    }
+    int reserve(size_t count, hipStream_t sync_first) {
+        if (p_ && cap_ >= count) return DICE_OK;
+        if (hipStreamSynchronize(sync_first) != hipSuccess) return fail(DICE_E_DEVICE, "hipStreamSynchronize failed");
+        return reserve(count);
+    }
+    void view(T* p, size_t count) {
+        reset();
+        p_ = p, cap_ = count, owned_ = false;
+    }
+    T* get() const { return p_; }
+    operator T*() const { return p_; }
+    T** arg() { return &p_; }   // a hipModuleLaunchKernel argument: the address of the stored pointer
+    DevBuf* operator&() = delete;   // ... which &buf would silently not be
+};
+using DevBytes = DevBuf<unsigned char>;
 
 }  // namespace dice
 
@@ -57,8 +121,10 @@ struct dice_ctx {
     int device = 0;
     int32_t T = 0, V = 0, w64 = 0, wq = 0, tpad = 0;
     hipStream_t stream = nullptr;
-    uint4* d_tq = nullptr;  // [wq][tpad] template quads (dense kernel)
-    int4* d_tc = nullptr;   // [tpad] TplConst (dense kernel)
+    // Device memory: every d_* field of the context and of the batch is a DevBuf, freed by the
+    // struct's destructor (ctx_free and dice_batch_destroy keep no list)
+    dice::DevBuf<uint4> d_tq;   // [wq][tpad] template quads (dense kernel)
+    dice::DevBuf<int4> d_tc;    // [tpad] TplConst (dense kernel)
     int32_t kind = 0;       // 0 dense, 1 sparse program, 2 LDS-tiled records, 3 postings (T > 64)
     dice::Program prog;     // sparse program (kind 1)
     hipModule_t module = nullptr;
@@ -68,24 +134,21 @@ struct dice_ctx {
     hipFunction_t prog_topk = nullptr;      // the ranking without the N x T rows, top-k <= 4
     hipFunction_t prog_topk16 = nullptr;    // top-k <= 16
     hipFunction_t prog_match_mfma = nullptr;   // prog_match with the matrix-core accumulate stage (prog.mfma)
-    int32_t* d_qperm = nullptr;             // sparse program tile slot -> vocabulary quad (kind 1)
+    dice::DevBuf<int32_t> d_qperm;          // sparse program tile slot -> vocabulary quad (kind 1)
     // Quads per file of the resident tile: wq (the row's quads) except for the sparse program's
     // compact tile, which the generated dice_pack_compact fills (dice_program.cpp).
     int32_t twq = 0;
     hipFunction_t prog_pack = nullptr;      // compact tile only
     dice_batch* scratch = nullptr;  // reused by the host-buffer calls
     // kind 2 plan (dice_lds.hip): per-(slab, template) entry runs, entries, wave split
-    void* d_lrec = nullptr;
-    void* d_lep = nullptr;
-    void* d_les = nullptr;
-    void* d_lwt = nullptr;
+    dice::DevBytes d_lrec, d_lep, d_lwt;
     int32_t lds_nslab = 0, lds_npass = 0;
     int64_t lds_entries = 0;
     // kind 3 plan (dice_post.hip): postings rows of the narrow words, dense-prefix masks
-    void* d_pdmt = nullptr;    // [20][kMfmaCols] u64 dense-prefix masks, word-major, zero-padded (MFMA kernel)
-    void* d_prow = nullptr;    // [64*w64][16] u16 postings row per word (short ids / long word ref)
-    void* d_povf = nullptr;    // flat u16 template ids of the long words
-    void* d_ptc = nullptr;     // [T] int4 template constants
+    dice::DevBytes d_pdmt;     // [20][kMfmaCols] u64 dense-prefix masks, word-major, zero-padded (MFMA kernel)
+    dice::DevBytes d_prow;     // [64*w64][16] u16 postings row per word (short ids / long word ref)
+    dice::DevBytes d_povf;     // flat u16 template ids of the long words
+    dice::DevBytes d_ptc;      // [T] int4 template constants
     int32_t post_dense = 0, post_tpad = 0, post_tp = 0, post_ld = 0;
     bool post_fast = false;
     int64_t post_rows = 0;
@@ -95,8 +158,7 @@ struct dice_ctx {
     uint32_t prune_max_lf = 0;       // largest template |Lf| (the long-file test of dice_match's routing)
     int32_t prune_long_route = 4;    // dice_match: postings kernels when >= 1/N of a batch's files are long (0: never)
     uint32_t prune_wf_noclamp = 0;   // |W_F| from which the bound's length term needs no clamp
-    void *d_p4q8 = nullptr, *d_p4tc = nullptr, *d_p4cc = nullptr, *d_p4off = nullptr, *d_p4rec = nullptr,
-         *d_p4slot = nullptr;
+    dice::DevBytes d_p4q8, d_p4tc, d_p4cc, d_p4off, d_p4rec, d_p4slot;
     int32_t p4_zkeep[2] = {-1, -1}, p4_zpos[2] = {0, 0};
     int32_t n_cu = 256, prune_max_evals = 8, prune_route = 16;
     // sharded calls (dice_shard.cpp): devices this ctx's device has peer access to (bit d), and
@@ -112,11 +174,11 @@ struct dice_ctx {
     // each one device region, mirrored by page-locked host regions -- one H2D and one D2H per call
     dice_batch* small = nullptr;
     void *h_small_in = nullptr, *h_small_out = nullptr;
-    void *d_ex_tbl = nullptr, *d_ex_need = nullptr, *d_ex_rec = nullptr;
+    dice::DevBytes d_ex_tbl, d_ex_need, d_ex_rec;
     bool exact_ready = false;
     // device wordset scan (dice_words.hip): the vocabulary table -- tagged slots, keys, lengths,
     // word offsets and bytes (for long words' tails)
-    void *d_wslots = nullptr, *d_wkeys = nullptr, *d_wlen = nullptr, *d_woff = nullptr, *d_wtxt = nullptr;
+    dice::DevBytes d_wslots, d_wkeys, d_wlen, d_woff, d_wtxt;
     uint32_t words_bmask = 0, words_id_bits = 0, words_extra = 0;
     bool words_ready = false;
 };
@@ -151,10 +213,6 @@ int download_match_to(dice_batch* b, int32_t* best, uint32_t* ov, double* score,
 int download_matrix_to(dice_batch* b, uint32_t* ov, double* score, int32_t* tki, double* tks, hipStream_t s,
                        hipMemcpyKind kind);
 int download_topk_to(dice_batch* b, int32_t* tki, double* tks, hipStream_t s, hipMemcpyKind kind);
-// the Exact tables (dice_exact.hip)
-void exact_free(dice_ctx* c);
-// the device wordset tables (dice_words.hip)
-void words_free(dice_ctx* c);
 // dice_batch_upload's tail: per-file scalars (wf == NULL: already on the device, b->n_long set;
 // len == NULL: already on the device), padding, and the tile repack (dice.hip)
 int upload_tail(dice_batch* b, int64_t n, const uint32_t* wf, const int32_t* len, const uint8_t* cc, hipStream_t s);
@@ -165,61 +223,54 @@ int repack(dice_batch* b, hipStream_t s);
 struct dice_batch {
     dice_ctx* ctx = nullptr;
     int64_t capacity = 0, n = 0, n_tiles_cap = 0;
-    uint64_t* d_rows = nullptr;     // staging [capacity][w64]
-    uint4* d_tiles = nullptr;       // [n_tiles][wq][64]
-    uint32_t* d_wf = nullptr;
-    int32_t* d_len = nullptr;
-    uint8_t* d_cc = nullptr;
-    int32_t* d_best = nullptr;
-    uint32_t* d_ov = nullptr;
-    double* d_score = nullptr;
-    // matrix results (lazily allocated)
-    int64_t mat_cap = 0;            // files the N x T buffers hold (0: not allocated)
-    int64_t tk_cap = 0;             // files the top-k buffers hold
-    int32_t mat_k = 0;              // k the top-k buffers hold
+    dice::DevBuf<uint64_t> d_rows;  // staging [capacity][w64]
+    dice::DevBuf<uint4> d_tiles;    // [n_tiles][wq][64]
+    dice::DevBuf<uint32_t> d_wf;
+    dice::DevBuf<int32_t> d_len;
+    dice::DevBuf<uint8_t> d_cc;
+    dice::DevBuf<int32_t> d_best;
+    dice::DevBuf<uint32_t> d_ov;
+    dice::DevBuf<double> d_score;
+    // matrix results (lazily allocated: [capacity][mat_ld] and [capacity][k] entries)
     int32_t k_used = 0;
     int32_t rank_mode = 0;          // last ranking call: 0 none, 1 dice_batch_matrix, 2 dice_batch_topk
     bool mat_rowmajor = false;      // kind 3 writes [n][ld] / [n][k] directly (no transpose)
     int32_t mat_ld = 0;             // row stride (templates) of the row-major matrix
-    uint32_t* d_mov = nullptr;      // template-major [T][capacity] (coalesced stores)
-    double* d_mscore = nullptr;     // template-major [T][capacity]
-    int32_t* d_tki = nullptr;
-    double* d_tks = nullptr;
-    void* d_stage = nullptr;        // row-major staging for downloads
-    void* d_pdense = nullptr;       // kind 3: dense-prefix partial overlaps [capacity][tp] u16
-    void* d_ids = nullptr;          // dice_batch_upload_ids staging: the id list ...
-    size_t ids_bytes = 0;
-    int64_t* d_offs = nullptr;      // ... and its [capacity + 1] offsets
-    size_t pdense_bytes = 0;
-    size_t stage_bytes = 0;
+    dice::DevBuf<uint32_t> d_mov;   // template-major [T][capacity] (coalesced stores)
+    dice::DevBuf<double> d_mscore;  // template-major [T][capacity]
+    dice::DevBuf<int32_t> d_tki;
+    dice::DevBuf<double> d_tks;
+    dice::DevBytes d_stage;         // row-major staging for downloads
+    dice::DevBytes d_pdense;        // kind 3: dense-prefix partial overlaps [capacity][tp] u16
+    dice::DevBytes d_ids;           // dice_batch_upload_ids staging: the id list ...
+    dice::DevBuf<int64_t> d_offs;   // ... and its [capacity + 1] offsets
     // pruned match (dice_prune.hip): files deferred to the postings kernels
-    int32_t* d_defer = nullptr;     // [capacity] file indices dice_prune4 deferred
-    uint32_t* d_ndefer = nullptr;   // their count
-    uint32_t* d_nscored = nullptr;  // per wave of the last pruned launch: (file, template) pairs scored exactly
+    dice::DevBuf<int32_t> d_defer;  // [capacity] file indices dice_prune4 deferred
+    dice::DevBuf<uint32_t> d_ndefer;   // their count
+    dice::DevBuf<uint32_t> d_nscored;  // per wave of the last pruned launch: (file, template) pairs scored exactly
     int64_t prune_waves = 0;        // waves of that launch (entries of d_nscored)
     int32_t last_match = 0;         // last match call: 0 none, 1 every pair scored, 2 bound-pruned
     int64_t n_long = 0;             // files of the upload with |W_F| above every template's |Lf| (-1: unknown)
     // Exact matcher (dice_batch_exact, lazily allocated): per-file result, field masks
-    int32_t* d_exact = nullptr;
-    uint64_t* d_fmask = nullptr;
+    dice::DevBuf<int32_t> d_exact;
+    dice::DevBuf<uint64_t> d_fmask;    // [capacity], from whichever of Exact, a text upload and set_rows comes first
     bool fmask_device = false;      // d_fmask holds the last upload's masks (dice_batch_upload_text)
     // dice_batch_upload_text (dice_words.hip): texts, their offsets and lengths, per-file status,
     // counters {overflowed files, long files}
-    uint8_t* d_text = nullptr;
-    size_t text_cap = 0;
-    int64_t* d_toff = nullptr;
-    int32_t* d_tlen = nullptr;
-    uint8_t* d_wstat = nullptr;
-    uint32_t* d_wcnt = nullptr;
+    dice::DevBuf<uint8_t> d_text;
+    dice::DevBuf<int64_t> d_toff;
+    dice::DevBuf<int32_t> d_tlen;
+    dice::DevBuf<uint8_t> d_wstat;
+    dice::DevBuf<uint32_t> d_wcnt;
     // dice_batch_content_hash (dice_hash.hip): 0 = the last upload left no text resident, 1 = the
     // texts of dice_batch_upload_text are resident, 2 = and their digests are computed (or queued)
     int32_t text_state = 0;
     // the resident texts are UTF-8 (dice_batch_upload_text_utf8; every other upload clears it): their
     // bytes are content_normalized's, so dice_batch_content_hash flags no file
     bool text_utf8 = false;
-    uint8_t* d_hdig = nullptr;      // [capacity][20] SHA-1 digests
-    uint8_t* d_hstat = nullptr;     // [capacity] 1 = one-byte-per-character text with a byte >= 0x80
-    uint32_t* d_hcnt = nullptr;     // the kernel's next-file counter
+    dice::DevBuf<uint8_t> d_hdig;   // [capacity][20] SHA-1 digests
+    dice::DevBuf<uint8_t> d_hstat;  // [capacity] 1 = one-byte-per-character text with a byte >= 0x80
+    dice::DevBuf<uint32_t> d_hcnt;  // the kernel's next-file counter
     // What has run since the last upload: every upload starts a new epoch, and a match, Exact or
     // project call records the epoch it ran in (dice_batch_projects reads the results of the first two)
     uint32_t epoch = 1, match_epoch = 0, exact_epoch = 0, proj_epoch = 0;
@@ -230,10 +281,40 @@ struct dice_batch {
     int64_t proj_cap = 0, proj_P = 0;
     int32_t proj_k = 0;
     bool proj_hash = false;         // the last resolve gathered the digests of dice_batch_content_hash
-    int64_t* d_poffs = nullptr;
-    uint8_t *d_pfflags = nullptr, *d_ptflags = nullptr, *d_pdig = nullptr;
-    int32_t *d_plic = nullptr, *d_pmf = nullptr, *d_pnl = nullptr, *d_plist = nullptr, *d_pmatcher = nullptr;
-    double* d_pconf = nullptr;
-    // small-call batch: d_wf/d_len/d_cc/d_rows carved from d_in, results from d_out
-    void *d_in = nullptr, *d_out = nullptr;
+    dice::DevBuf<int64_t> d_poffs;
+    dice::DevBuf<uint8_t> d_pfflags, d_ptflags, d_pdig;
+    dice::DevBuf<int32_t> d_plic, d_pmf, d_pnl, d_plist, d_pmatcher;
+    dice::DevBuf<double> d_pconf;
+    // small-call batch: d_wf/d_len/d_cc/d_rows are views into d_in, the results views into d_out
+    dice::DevBytes d_in, d_out;
 };
+
+namespace dice {
+
+inline hipStream_t stream_of(dice_ctx* c, void* s) { return s ? (hipStream_t)s : c->stream; }
+
+// A new upload of n files starts: what the last one left (long-file count, device masks, resident
+// texts and their form) is gone, and so is every result (a new epoch).
+inline void begin_upload(dice_batch* b, int64_t n) {
+    b->n = n;
+    b->n_long = 0;
+    b->fmask_device = false;
+    b->text_state = 0;
+    ++b->epoch;
+    b->text_utf8 = false;
+}
+
+// files with |W_F| above every template's |Lf| (the long-file test of dice_match's routing)
+inline int64_t count_long(const dice_ctx* c, const uint32_t* wf, int64_t n) {
+    int64_t n_long = 0;
+    if (c->prune)
+        for (int64_t i = 0; i < n; ++i) n_long += wf[i] > c->prune_max_lf;
+    return n_long;
+}
+
+inline int check_files(const dice_files* f) {
+    if (!f->bits || !f->wordset_size || !f->length || !f->cc_false_positive) return fail(DICE_E_ARG, "NULL file arrays");
+    return DICE_OK;
+}
+
+}  // namespace dice

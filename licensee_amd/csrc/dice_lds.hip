@@ -322,9 +322,8 @@ int lds_setup(dice_ctx* c, const dice_templates* t) {
         wt.insert(wt.end(), w.begin(), w.end());
     }
     int rc;
-    if ((rc = dalloc_bytes(&c->d_lrec, rec.size() * sizeof(int32_t))) ||
-        (rc = dalloc_bytes(&c->d_lep, ep.size() * sizeof(uint4))) ||
-        (rc = dalloc_bytes(&c->d_lwt, wt.size() * sizeof(int32_t))))
+    if ((rc = c->d_lrec.reserve(rec.size() * sizeof(int32_t))) || (rc = c->d_lep.reserve(ep.size() * sizeof(uint4))) ||
+        (rc = c->d_lwt.reserve(wt.size() * sizeof(int32_t))))
         return rc;
     if (hipMemcpy(c->d_lrec, rec.data(), rec.size() * sizeof(int32_t), hipMemcpyHostToDevice) != hipSuccess ||
         hipMemcpy(c->d_lep, ep.data(), ep.size() * sizeof(uint4), hipMemcpyHostToDevice) != hipSuccess ||
@@ -341,8 +340,8 @@ int lds_launch_match(dice_ctx* c, dice_batch* b, double thr, hipStream_t s) {
     const int64_t n_tiles = (b->n + kWave - 1) / kWave;
     const int64_t groups = (n_tiles + kTiles - 1) / kTiles;
     hipLaunchKernelGGL((dice_lds_match<kG>), dim3((unsigned)groups), dim3(kLdsWaves * kWave), 0, s, b->d_tiles, b->n,
-                       c->wq, c->lds_nslab, c->T, (const int32_t*)c->d_lrec, (const uint4*)c->d_lep,
-                       (const int32_t*)c->d_lwt, c->lds_npass, c->d_tc, b->d_wf, b->d_len, b->d_cc, thr, b->d_best,
+                       c->wq, c->lds_nslab, c->T, (const int32_t*)c->d_lrec.get(), (const uint4*)c->d_lep.get(),
+                       (const int32_t*)c->d_lwt.get(), c->lds_npass, c->d_tc, b->d_wf, b->d_len, b->d_cc, thr, b->d_best,
                        b->d_ov, b->d_score);
     return hipGetLastError() == hipSuccess ? DICE_OK : fail(DICE_E_DEVICE, "dice_lds_match launch failed");
 }

@@ -930,8 +930,8 @@ int post_setup(dice_ctx* c, const dice_templates* t) {
     for (int32_t i = 0; i < T; ++i)
         for (int d = 0; d < D; ++d) dmt[(size_t)d * kMfmaCols + i] = t->lf_bits[(size_t)i * w64 + d];
     int rc;
-    if ((rc = dalloc_bytes(&c->d_prow, prow.size() * 2)) || (rc = dalloc_bytes(&c->d_povf, plong.size() * 2)) ||
-        (rc = dalloc_bytes(&c->d_ptc, tcv.size() * sizeof(uint2))) || (rc = dalloc_bytes(&c->d_pdmt, dmt.size() * 8)))
+    if ((rc = c->d_prow.reserve(prow.size() * 2)) || (rc = c->d_povf.reserve(plong.size() * 2)) ||
+        (rc = c->d_ptc.reserve(tcv.size() * sizeof(uint2))) || (rc = c->d_pdmt.reserve(dmt.size() * 8)))
         return rc;
     if (hipMemcpy(c->d_pdmt, dmt.data(), dmt.size() * 8, hipMemcpyHostToDevice) != hipSuccess ||
         hipMemcpy(c->d_povf, plong.data(), plong.size() * 2, hipMemcpyHostToDevice) != hipSuccess ||
@@ -970,23 +970,12 @@ static void launch_dense(dice_ctx* c, dice_batch* b, hipStream_t s, int64_t grou
     const int64_t mtiles = (b->n + 32 * mt - 1) / (32 * mt);
     const int64_t g = std::min<int64_t>(std::min<int64_t>(groups, mtiles), (int64_t)c->n_cu);
     hipLaunchKernelGGL(kern, dim3((unsigned)g), dim3((small ? 12 : 11) * kWave), 0, s, (const uint64_t*)b->d_rows,
-                       b->n, c->w64, c->post_dense, c->post_tp, (const uint64_t*)c->d_pdmt,
-                       reinterpret_cast<uint16_t*>(b->d_pdense), idx, pn);
+                       b->n, c->w64, c->post_dense, c->post_tp, (const uint64_t*)c->d_pdmt.get(),
+                       reinterpret_cast<uint16_t*>(b->d_pdense.get()), idx, pn);
 }
 
 // The batch's dense partials, [capacity][tp] u16 rows.
-int post_reserve(dice_ctx* c, dice_batch* b) {
-    const size_t need = (size_t)b->capacity * c->post_tp * 2;
-    if (b->pdense_bytes < need) {
-        if (b->d_pdense) (void)hipFree(b->d_pdense);
-        b->d_pdense = nullptr;
-        b->pdense_bytes = 0;
-        int rc = dalloc_bytes(&b->d_pdense, need);
-        if (rc) return rc;
-        b->pdense_bytes = need;
-    }
-    return DICE_OK;
-}
+int post_reserve(dice_ctx* c, dice_batch* b) { return b->d_pdense.reserve((size_t)b->capacity * c->post_tp * 2); }
 
 // idx/pn (match mode only): score the *pn files idx[0..*pn) of the batch (the pruned match's
 // deferred files) on persistent grids; nothing is read back on the host.
@@ -999,7 +988,7 @@ static int launch(dice_ctx* c, dice_batch* b, double thr, int32_t k, hipStream_t
     // (the narrow kernel's workgroups resident per CU: two 16-wave, three 8-wave)
     constexpr int kNarrowWaves = narrow_waves<kMatrix>();
     const int64_t groups = idx ? std::min<int64_t>(tiles, (kNarrowWaves == 16 ? 2 : 3) * (int64_t)c->n_cu) : tiles;
-    uint16_t* part16 = reinterpret_cast<uint16_t*>(b->d_pdense);
+    uint16_t* part16 = reinterpret_cast<uint16_t*>(b->d_pdense.get());
     if (c->post_dense == 0 || (POST_DIAG & 1)) {
         // no dense prefix: zero partials
         const size_t rows = (size_t)(idx ? b->capacity : b->n);
@@ -1021,9 +1010,9 @@ static int launch(dice_ctx* c, dice_batch* b, double thr, int32_t k, hipStream_t
                                 : dice_post_narrow_topk<kPostMaxTpad>);
     hipLaunchKernelGGL(kern, dim3((unsigned)groups), dim3(kNarrowWaves * kWave), 0, s,
                        (const uint64_t*)b->d_rows, b->n, c->w64, c->post_dense, c->T, c->post_tp,
-                       part16, (const uint16_t*)c->d_prow, (const uint16_t*)c->d_povf,
-                       (const uint2*)c->d_ptc, b->d_wf, b->d_len, b->d_cc, thr, b->d_best, b->d_ov, b->d_score, k,
-                       kRows ? b->d_mov : nullptr, kRows ? b->d_mscore : nullptr, k > 0 ? b->d_tki : nullptr, b->d_tks,
+                       part16, (const uint16_t*)c->d_prow.get(), (const uint16_t*)c->d_povf.get(),
+                       (const uint2*)c->d_ptc.get(), b->d_wf, b->d_len, b->d_cc, thr, b->d_best, b->d_ov, b->d_score, k,
+                       kRows ? b->d_mov.get() : nullptr, kRows ? b->d_mscore.get() : nullptr, k > 0 ? b->d_tki.get() : nullptr, b->d_tks,
                        c->post_fast, idx,
                        pn, c->post_ld);
     return hipGetLastError() == hipSuccess ? DICE_OK : fail(DICE_E_DEVICE, "dice_post kernels launch failed");

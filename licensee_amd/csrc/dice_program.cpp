@@ -156,7 +156,7 @@ int program_setup(dice_ctx* c, const dice_templates* t) {
         if (!get(&c->prog_pack, "dice_pack_compact")) return fail(DICE_E_DEVICE, "hipModuleGetFunction failed");
     } else {                // dice_pack_tiles (dice.hip) applies the permutation
         const size_t bytes = p.sched.qperm.size() * sizeof(int32_t);
-        if ((rc = dalloc_bytes(reinterpret_cast<void**>(&c->d_qperm), bytes)) != DICE_OK) return rc;
+        if ((rc = c->d_qperm.reserve(p.sched.qperm.size())) != DICE_OK) return rc;
         if (hipMemcpy(c->d_qperm, p.sched.qperm.data(), bytes, hipMemcpyHostToDevice) != hipSuccess)
             return fail(DICE_E_DEVICE, "program tile permutation upload failed");
     }
@@ -168,7 +168,7 @@ int program_setup(dice_ctx* c, const dice_templates* t) {
 int program_launch_pack(dice_ctx* c, dice_batch* b, int64_t n, hipStream_t s) {
     const int64_t n_tiles = (n + 63) / 64;
     if (n_tiles == 0) return DICE_OK;
-    void* args[] = {&b->d_rows, &n, &b->d_tiles};
+    void* args[] = {b->d_rows.arg(), &n, b->d_tiles.arg()};
     if (hipModuleLaunchKernel(c->prog_pack, (unsigned)n_tiles, 1, 1, 256, 1, 1, 0, s, args, nullptr) != hipSuccess)
         return fail(DICE_E_DEVICE, "launch dice_pack_compact failed");
     return DICE_OK;
@@ -184,7 +184,8 @@ int program_launch_match(dice_ctx* c, dice_batch* b, double thr, hipStream_t s) 
         threads = 64 * kMfmaMatchWaves;
     }
     int64_t n = b->n;
-    void* args[] = {&b->d_tiles, &n, &b->d_wf, &b->d_len, &b->d_cc, &thr, &b->d_best, &b->d_ov, &b->d_score};
+    void* args[] = {b->d_tiles.arg(), &n, b->d_wf.arg(), b->d_len.arg(), b->d_cc.arg(), &thr, b->d_best.arg(),
+                    b->d_ov.arg(), b->d_score.arg()};
     if (hipModuleLaunchKernel(fn, grid, 1, 1, threads, 1, 1, 0, s, args, nullptr) != hipSuccess)
         return fail(DICE_E_DEVICE, "launch dice_prog_match failed");
     return DICE_OK;
@@ -196,9 +197,10 @@ int program_launch_matrix(dice_ctx* c, dice_batch* b, int32_t k, hipStream_t s) 
     const unsigned grid = (unsigned)((n_tiles + wpb - 1) / wpb);
     int64_t n = b->n;
     int32_t kk = k;
-    int32_t* tki = k > 0 ? b->d_tki : nullptr;
-    double* tks = k > 0 ? b->d_tks : nullptr;
-    void* args[] = {&b->d_tiles, &n, &b->d_wf, &b->d_len, &b->d_cc, &kk, &b->d_mov, &b->d_mscore, &tki, &tks};
+    int32_t* tki = k > 0 ? b->d_tki.get() : nullptr;
+    double* tks = k > 0 ? b->d_tks.get() : nullptr;
+    void* args[] = {b->d_tiles.arg(), &n, b->d_wf.arg(), b->d_len.arg(), b->d_cc.arg(), &kk, b->d_mov.arg(),
+                    b->d_mscore.arg(), &tki, &tks};
     hipFunction_t fn = k <= 4 ? c->prog_matrix : c->prog_matrix16;
     if (hipModuleLaunchKernel(fn, grid, 1, 1, 64 * wpb, 1, 1, 0, s, args, nullptr) != hipSuccess)
         return fail(DICE_E_DEVICE, "launch dice_prog_matrix failed");
@@ -211,7 +213,7 @@ int program_launch_topk(dice_ctx* c, dice_batch* b, int32_t k, hipStream_t s) {
     const unsigned grid = (unsigned)((n_tiles + wpb - 1) / wpb);
     int64_t n = b->n;
     int32_t kk = k;
-    void* args[] = {&b->d_tiles, &n, &b->d_wf, &b->d_len, &b->d_cc, &kk, &b->d_tki, &b->d_tks};
+    void* args[] = {b->d_tiles.arg(), &n, b->d_wf.arg(), b->d_len.arg(), b->d_cc.arg(), &kk, b->d_tki.arg(), b->d_tks.arg()};
     // the VALU program under every DICE_PROG_MATCH: the matrix-core stage measured slower here too
     // (DESIGN.md Appendix B), the k sorted slots' offers bound the kernel, not the accumulation
     hipFunction_t fn = k <= 4 ? c->prog_topk : c->prog_topk16;

@@ -232,27 +232,6 @@ __global__ __launch_bounds__(kWave) void dice_project_kernel(ProjIn in, const in
     }
 }
 
-namespace {
-
-struct PGuard {
-    int prev = -1;
-    explicit PGuard(int dev) {
-        if (hipGetDevice(&prev) != hipSuccess) prev = -1;
-        (void)hipSetDevice(dev);
-    }
-    ~PGuard() {
-        if (prev >= 0) (void)hipSetDevice(prev);
-    }
-};
-
-template <typename T>
-int regrow(T** p, size_t bytes) {
-    if (*p) (void)hipFree(*p);
-    *p = nullptr;
-    return dalloc_bytes(reinterpret_cast<void**>(p), bytes);
-}
-
-}  // namespace
 }  // namespace dice
 
 using dice::fail;
@@ -277,25 +256,23 @@ int dice_batch_projects(dice_batch* b, int64_t P, const int64_t* offsets, const 
     if (b->match_epoch != b->epoch) return fail(DICE_E_STATE, "no match call has run since the last upload");
     if (use_exact && b->exact_epoch != b->epoch)
         return fail(DICE_E_STATE, "use_exact needs dice_batch_exact to have run since the last upload");
-    dice::PGuard g(c->device);
-    hipStream_t s = stream ? (hipStream_t)stream : c->stream;
+    dice::DeviceGuard g(c->device);
+    hipStream_t s = dice::stream_of(c, stream);
     b->proj_epoch = 0;
     int rc;
     if (P > b->proj_cap || !b->d_poffs) {
-        // (the buffers may still feed an earlier resolve or its download)
+        // (the buffers may still feed an earlier resolve or its download; proj_cap stays 0 while a
+        // regrow is in flight)
         if (hipStreamSynchronize(s) != hipSuccess) return fail(DICE_E_DEVICE, "hipStreamSynchronize failed");
-        const int64_t cap = std::max<int64_t>(std::max<int64_t>(P, 2 * b->proj_cap), 64);
+        const size_t cap = (size_t)std::max<int64_t>(std::max<int64_t>(P, 2 * b->proj_cap), 64);
         b->proj_cap = 0;
-        if ((rc = dice::regrow(&b->d_poffs, (size_t)(cap + 1) * 8)) || (rc = dice::regrow(&b->d_plic, (size_t)cap * 4)) ||
-            (rc = dice::regrow(&b->d_pmf, (size_t)cap * 4)) || (rc = dice::regrow(&b->d_pnl, (size_t)cap * 4)) ||
-            (rc = dice::regrow(&b->d_plist, (size_t)cap * DICE_PROJECT_K_MAX * 4)) ||
-            (rc = dice::regrow(&b->d_pmatcher, (size_t)cap * 4)) || (rc = dice::regrow(&b->d_pconf, (size_t)cap * 8)) ||
-            (rc = dice::regrow(&b->d_pdig, (size_t)cap * 20)))
+        if ((rc = b->d_poffs.reserve(cap + 1)) || (rc = b->d_plic.reserve(cap)) || (rc = b->d_pmf.reserve(cap)) ||
+            (rc = b->d_pnl.reserve(cap)) || (rc = b->d_plist.reserve(cap * DICE_PROJECT_K_MAX)) ||
+            (rc = b->d_pmatcher.reserve(cap)) || (rc = b->d_pconf.reserve(cap)) || (rc = b->d_pdig.reserve(cap * 20)))
             return rc;
-        b->proj_cap = cap;
+        b->proj_cap = (int64_t)cap;
     }
-    if (!b->d_pfflags && (rc = dice::dalloc_bytes(reinterpret_cast<void**>(&b->d_pfflags), (size_t)b->capacity))) return rc;
-    if (!b->d_ptflags && (rc = dice::dalloc_bytes(reinterpret_cast<void**>(&b->d_ptflags), (size_t)c->T))) return rc;
+    if ((rc = b->d_pfflags.reserve((size_t)b->capacity)) || (rc = b->d_ptflags.reserve((size_t)c->T))) return rc;
     b->proj_P = P;
     b->proj_k = k;
     b->proj_hash = b->text_state == 2;   // the digests of dice_batch_content_hash are there to gather
@@ -305,15 +282,15 @@ int dice_batch_projects(dice_batch* b, int64_t P, const int64_t* offsets, const 
             hipMemcpyAsync(b->d_ptflags, template_flags, (size_t)c->T, hipMemcpyHostToDevice, s) != hipSuccess)
             return fail(DICE_E_DEVICE, "project offsets/flags upload failed");
         dice::ProjIn in;
-        in.exact = use_exact ? b->d_exact : nullptr;
+        in.exact = use_exact ? b->d_exact.get() : nullptr;
         in.best = b->d_best;
         in.fflags = b->d_pfflags;
         in.tflags = b->d_ptflags;
         in.T = c->T;
         const unsigned grid = (unsigned)((P + dice::kWave - 1) / dice::kWave);
         hipLaunchKernelGGL(dice::dice_project_kernel, dim3(grid), dim3(dice::kWave), lds, s, in, (const int64_t*)b->d_poffs, P,
-                           k, (const double*)b->d_score, b->proj_hash ? (const uint32_t*)b->d_hdig : nullptr, b->d_plic,
-                           b->d_pmf, b->d_pnl, b->d_plist, b->d_pmatcher, b->d_pconf, (uint32_t*)b->d_pdig);
+                           k, (const double*)b->d_score, b->proj_hash ? (const uint32_t*)b->d_hdig.get() : nullptr, b->d_plic,
+                           b->d_pmf, b->d_pnl, b->d_plist, b->d_pmatcher, b->d_pconf, (uint32_t*)b->d_pdig.get());
         if (hipGetLastError() != hipSuccess) return fail(DICE_E_DEVICE, "dice_project_kernel launch failed");
     }
     b->proj_epoch = b->epoch;
@@ -331,8 +308,8 @@ int dice_batch_download_projects(dice_batch* b, int32_t* license, int32_t* match
     int rc = projects_ready(b);
     if (rc) return rc;
     dice_ctx* c = b->ctx;
-    dice::PGuard g(c->device);
-    hipStream_t s = stream ? (hipStream_t)stream : c->stream;
+    dice::DeviceGuard g(c->device);
+    hipStream_t s = dice::stream_of(c, stream);
     const size_t P = (size_t)b->proj_P, k = (size_t)b->proj_k;
     if (P && ((license && hipMemcpyAsync(license, b->d_plic, P * 4, hipMemcpyDeviceToHost, s) != hipSuccess) ||
               (matched_file && hipMemcpyAsync(matched_file, b->d_pmf, P * 4, hipMemcpyDeviceToHost, s) != hipSuccess) ||
@@ -348,8 +325,8 @@ int dice_batch_download_project_match(dice_batch* b, int32_t* matcher, double* c
     if (digest && !b->proj_hash)
         return fail(DICE_E_STATE, "no content hash was computed before the project resolve");
     dice_ctx* c = b->ctx;
-    dice::PGuard g(c->device);
-    hipStream_t s = stream ? (hipStream_t)stream : c->stream;
+    dice::DeviceGuard g(c->device);
+    hipStream_t s = dice::stream_of(c, stream);
     const size_t P = (size_t)b->proj_P;
     if (P && ((matcher && hipMemcpyAsync(matcher, b->d_pmatcher, P * 4, hipMemcpyDeviceToHost, s) != hipSuccess) ||
               (confidence && hipMemcpyAsync(confidence, b->d_pconf, P * 8, hipMemcpyDeviceToHost, s) != hipSuccess) ||

@@ -612,9 +612,9 @@ int prune_setup(dice_ctx* c, const dice_templates* t) {
         if (!t->is_cc[i] && i > zk[1]) zk[1] = i, zp[1] = p;
     }
     int rc;
-    if ((rc = dalloc_bytes(&c->d_p4q8, q8p.size() * 4)) || (rc = dalloc_bytes(&c->d_p4tc, tcp.size() * 16)) ||
-        (rc = dalloc_bytes(&c->d_p4cc, ccp.size() * 4)) || (rc = dalloc_bytes(&c->d_p4off, srec.size() * 4)) ||
-        (rc = dalloc_bytes(&c->d_p4rec, recp.size() * 16)) || (rc = dalloc_bytes(&c->d_p4slot, slot.size() * 16)))
+    if ((rc = c->d_p4q8.reserve(q8p.size() * 4)) || (rc = c->d_p4tc.reserve(tcp.size() * 16)) ||
+        (rc = c->d_p4cc.reserve(ccp.size() * 4)) || (rc = c->d_p4off.reserve(srec.size() * 4)) ||
+        (rc = c->d_p4rec.reserve(recp.size() * 16)) || (rc = c->d_p4slot.reserve(slot.size() * 16)))
         return rc;
     if (hipMemcpy(c->d_p4q8, q8p.data(), q8p.size() * 4, hipMemcpyHostToDevice) != hipSuccess ||
         hipMemcpy(c->d_p4tc, tcp.data(), tcp.size() * 16, hipMemcpyHostToDevice) != hipSuccess ||
@@ -673,12 +673,12 @@ static int launch_prune(dice_ctx* c, dice_batch* b, double thr, hipStream_t s, f
     const int32_t max_evals = c->prune_max_evals == 0 ? INT32_MAX : c->prune_max_evals;
     const int32_t route = c->prune_max_evals == 0 ? INT32_MAX : c->prune_route;
     Prune4Args pa;
-    pa.q8 = (const uint4*)c->d_p4q8;
-    pa.tc = (const uint4*)c->d_p4tc;
-    pa.ccm = (const uint32_t*)c->d_p4cc;
-    pa.srec = (const uint32_t*)c->d_p4off;
-    pa.qrec = (const uint4*)c->d_p4rec;
-    pa.slot = (const uint4*)c->d_p4slot;
+    pa.q8 = (const uint4*)c->d_p4q8.get();
+    pa.tc = (const uint4*)c->d_p4tc.get();
+    pa.ccm = (const uint32_t*)c->d_p4cc.get();
+    pa.srec = (const uint32_t*)c->d_p4off.get();
+    pa.qrec = (const uint4*)c->d_p4rec.get();
+    pa.slot = (const uint4*)c->d_p4slot.get();
     for (int k = 0; k < 2; ++k) {
         pa.zkeep[k] = c->p4_zkeep[k];
         pa.zpos[k] = c->p4_zpos[k];
@@ -726,12 +726,10 @@ static int launch_prune_j(dice_ctx* c, dice_batch* b, double thr, hipStream_t s,
 // file list + count, and the postings pass's dense partials.
 int prune_reserve(dice_ctx* c, dice_batch* b) {
     int rc;
-    // the device list of deferred files and its length
-    if (!b->d_defer && ((rc = dalloc_bytes((void**)&b->d_defer, (size_t)b->capacity * 4)) ||
-                        (rc = dalloc_bytes((void**)&b->d_ndefer, 4))))
-        return rc;
-    // one exact-score count per wave of each persistent grid (at most 32 waves per CU each)
-    if (!b->d_nscored && (rc = dalloc_bytes((void**)&b->d_nscored, (size_t)std::max(c->n_cu, 1) * 64 * 4 + 128 * 4)))
+    // the device list of deferred files and its length; one exact-score count per wave of each
+    // persistent grid (at most 32 waves per CU each)
+    if ((rc = b->d_defer.reserve((size_t)b->capacity)) || (rc = b->d_ndefer.reserve(1)) ||
+        (rc = b->d_nscored.reserve((size_t)std::max(c->n_cu, 1) * 64 + 128)))
         return rc;
     return post_reserve(c, b);
 }

@@ -125,7 +125,7 @@ int upload_shard(dice_ctx* c, dice_batch* b, const dice_files* part) {
     const int64_t per = (int64_t)(c->h_stage_bytes / row);
     if (per < 1) return dice_batch_upload(b, part, nullptr);
     const char* src = reinterpret_cast<const char*>(part->bits);
-    char* dst = reinterpret_cast<char*>(b->d_rows);
+    char* dst = reinterpret_cast<char*>(b->d_rows.get());
     int k = 0;
     for (int64_t f0 = 0; f0 < part->n_files; f0 += per, k ^= 1) {
         const size_t nb = (size_t)std::min<int64_t>(per, part->n_files - f0) * row;
@@ -174,25 +174,17 @@ void prepare_device_gather(dice_ctx* const* ctxs, int32_t n_ctx) {
     g_last_gather_peer = !remote ? -1 : all ? 1 : 0;
 }
 
-// Device gather buffer on ctxs[0]'s device: `bytes` bytes, freed by the caller.
-int gather_alloc(dice_ctx* c0, size_t bytes, void** p) {
-    int prev = -1;
-    (void)hipGetDevice(&prev);
-    if (hipSetDevice(c0->device) != hipSuccess) return fail(DICE_E_DEVICE, "hipSetDevice failed");
-    const hipError_t e = hipMalloc(p, bytes ? bytes : 1);
-    if (prev >= 0) (void)hipSetDevice(prev);
-    if (e != hipSuccess) {
-        *p = nullptr;
-        return fail(DICE_E_NOMEM, "gather buffer allocation failed");
-    }
-    return DICE_OK;
+// Device gather buffer on ctxs[0]'s device: `bytes` bytes, owned by the caller's `buf`.
+int gather_alloc(dice_ctx* c0, size_t bytes, dice::DevBytes& buf) {
+    dice::DeviceGuard g(c0->device);
+    if (!g.ok) return fail(DICE_E_DEVICE, "hipSetDevice failed");
+    return buf.reserve(bytes);
 }
 
 // One D2H per output array from the device gather buffer (regions laid out back to back).
 int gather_d2h(dice_ctx* c0, const std::vector<std::pair<void*, size_t>>& outs, char* dev) {
-    int prev = -1;
-    (void)hipGetDevice(&prev);
-    if (hipSetDevice(c0->device) != hipSuccess) return fail(DICE_E_DEVICE, "hipSetDevice failed");
+    dice::DeviceGuard g(c0->device);
+    if (!g.ok) return fail(DICE_E_DEVICE, "hipSetDevice failed");
     size_t off = 0;
     hipError_t e = hipSuccess;
     for (auto& o : outs) {
@@ -200,7 +192,6 @@ int gather_d2h(dice_ctx* c0, const std::vector<std::pair<void*, size_t>>& outs, 
         off += o.second;
     }
     if (e == hipSuccess) e = hipStreamSynchronize(c0->stream);
-    if (prev >= 0) (void)hipSetDevice(prev);
     return e == hipSuccess ? DICE_OK : fail(DICE_E_DEVICE, std::string("gather D2H: ") + hipGetErrorString(e));
 }
 
@@ -212,14 +203,15 @@ static int match_sharded(dice_ctx* const* ctxs, int32_t n_ctx, const dice_files*
     if (rc) return rc;
     const int64_t n = f->n_files;
     if (n == 0) return DICE_OK;
-    if (!f->bits || !f->wordset_size || !f->length || !f->cc_false_positive) return fail(DICE_E_ARG, "NULL file arrays");
+    if ((rc = dice::check_files(f))) return rc;
     const int32_t w64 = ctxs[0]->w64;
-    char* dev = nullptr;
+    dice::DevBytes gbuf;
     g_last_gather_peer = -1;
     if (gather == DICE_GATHER_DEVICE) {
-        if ((rc = gather_alloc(ctxs[0], (size_t)n * 16, (void**)&dev))) return rc;
+        if ((rc = gather_alloc(ctxs[0], (size_t)n * 16, gbuf))) return rc;
         prepare_device_gather(ctxs, n_ctx);
     }
+    char* dev = (char*)gbuf.get();
     // device gather layout: best [n] i32 | overlap [n] u32 | score [n] f64
     int32_t* g_best = dev ? (int32_t*)dev : nullptr;
     uint32_t* g_ov = dev ? (uint32_t*)(dev + (size_t)n * 4) : nullptr;
@@ -241,7 +233,6 @@ static int match_sharded(dice_ctx* const* ctxs, int32_t n_ctx, const dice_files*
     });
     if (rc == DICE_OK && dev)
         rc = gather_d2h(ctxs[0], {{best, (size_t)n * 4}, {ov, (size_t)n * 4}, {score, (size_t)n * 8}}, dev);
-    if (dev) (void)hipFree(dev);
     return rc;
 }
 
@@ -265,18 +256,19 @@ int dice_similarity_matrix_sharded(dice_ctx* const* ctxs, int32_t n_ctx, const d
     if (k > 0 && (!tki || !tks)) return fail(DICE_E_ARG, "top-k outputs required when k > 0");
     const int64_t n = f->n_files;
     if (n == 0) return DICE_OK;
-    if (!f->bits || !f->wordset_size || !f->length || !f->cc_false_positive) return fail(DICE_E_ARG, "NULL file arrays");
+    if ((rc = dice::check_files(f))) return rc;
     const int32_t w64 = ctxs[0]->w64, T = ctxs[0]->T;
     if (k == 0) tki = nullptr, tks = nullptr;
     // device gather layout (row-major, as the ABI): overlap [n][T] u32 | score [n][T] f64 |
     // top-k index [n][k] i32 | top-k score [n][k] f64
     const size_t b_ov = (size_t)n * T * 4, b_sc = (size_t)n * T * 8, b_ki = (size_t)n * k * 4, b_ks = (size_t)n * k * 8;
-    char* dev = nullptr;
+    dice::DevBytes gbuf;
     g_last_gather_peer = -1;
     if (gather == DICE_GATHER_DEVICE) {
-        if ((rc = gather_alloc(ctxs[0], b_ov + b_sc + b_ki + b_ks, (void**)&dev))) return rc;
+        if ((rc = gather_alloc(ctxs[0], b_ov + b_sc + b_ki + b_ks, gbuf))) return rc;
         prepare_device_gather(ctxs, n_ctx);
     }
+    char* dev = (char*)gbuf.get();
     rc = run_shards(ctxs, n_ctx, n, [&](int32_t i, Shard& s) {
         dice_ctx* c = ctxs[i];
         dice_batch* b = nullptr;
@@ -300,7 +292,6 @@ int dice_similarity_matrix_sharded(dice_ctx* const* ctxs, int32_t n_ctx, const d
     });
     if (rc == DICE_OK && dev)
         rc = gather_d2h(ctxs[0], {{ov, b_ov}, {score, b_sc}, {tki, b_ki}, {tks, b_ks}}, dev);
-    if (dev) (void)hipFree(dev);
     return rc;
 }
 
@@ -312,16 +303,17 @@ int dice_topk_sharded(dice_ctx* const* ctxs, int32_t n_ctx, const dice_files* f,
     if (!tki || !tks) return fail(DICE_E_ARG, "top-k outputs required");
     const int64_t n = f->n_files;
     if (n == 0) return DICE_OK;
-    if (!f->bits || !f->wordset_size || !f->length || !f->cc_false_positive) return fail(DICE_E_ARG, "NULL file arrays");
+    if ((rc = dice::check_files(f))) return rc;
     const int32_t w64 = ctxs[0]->w64;
     // device gather layout (row-major, as the ABI): top-k index [n][k] i32 | top-k score [n][k] f64
     const size_t b_ki = (size_t)n * k * 4, b_ks = (size_t)n * k * 8;
-    char* dev = nullptr;
+    dice::DevBytes gbuf;
     g_last_gather_peer = -1;
     if (gather == DICE_GATHER_DEVICE) {
-        if ((rc = gather_alloc(ctxs[0], b_ki + b_ks, (void**)&dev))) return rc;
+        if ((rc = gather_alloc(ctxs[0], b_ki + b_ks, gbuf))) return rc;
         prepare_device_gather(ctxs, n_ctx);
     }
+    char* dev = (char*)gbuf.get();
     rc = run_shards(ctxs, n_ctx, n, [&](int32_t i, Shard& s) {
         dice_ctx* c = ctxs[i];
         dice_batch* b = nullptr;
@@ -336,7 +328,6 @@ int dice_topk_sharded(dice_ctx* const* ctxs, int32_t n_ctx, const dice_files* f,
         return dice::download_topk_to(b, tki + lo * k, tks + lo * k, c->stream, hipMemcpyDeviceToHost);
     });
     if (rc == DICE_OK && dev) rc = gather_d2h(ctxs[0], {{tki, b_ki}, {tks, b_ks}}, dev);
-    if (dev) (void)hipFree(dev);
     return rc;
 }
 

@@ -709,37 +709,7 @@ __global__ __launch_bounds__(kCharsWaves * kWave) void dice_text_chars_kernel(
 
 namespace dice {
 
-void words_free(dice_ctx* c) {
-    void* p[] = {c->d_wslots, c->d_wkeys, c->d_wlen, c->d_woff, c->d_wtxt};
-    for (void* x : p)
-        if (x) (void)hipFree(x);
-    c->d_wslots = c->d_wkeys = c->d_wlen = c->d_woff = c->d_wtxt = nullptr;
-    c->words_ready = false;
-}
-
 namespace {
-
-struct WGuard {
-    int prev = -1;
-    explicit WGuard(int dev) {
-        if (hipGetDevice(&prev) != hipSuccess) prev = -1;
-        (void)hipSetDevice(dev);
-    }
-    ~WGuard() {
-        if (prev >= 0) (void)hipSetDevice(prev);
-    }
-};
-
-template <class T>
-int grow(T** p, size_t& cap, size_t need) {
-    if (*p && cap >= need) return DICE_OK;
-    if (*p) (void)hipFree(*p);
-    *p = nullptr;
-    cap = 0;
-    int rc = dalloc_bytes(reinterpret_cast<void**>(p), need);
-    if (!rc) cap = need;
-    return rc;
-}
 
 void host_key(const std::string& w, uint64_t& lo, uint64_t& hi, uint32_t& tail) {
     lo = hi = 0;
@@ -829,12 +799,13 @@ int dice_vocab_setup(dice_ctx* c, int32_t n_words, const char* const* words, int
         }
     }
     if (txt.empty()) txt.push_back(0);
-    dice::WGuard g(c->device);
-    dice::words_free(c);
+    dice::DeviceGuard g(c->device);
+    c->words_ready = false;   // the old tables go whether or not the new ones arrive
+    c->d_wslots.reset(), c->d_wkeys.reset(), c->d_wlen.reset(), c->d_woff.reset(), c->d_wtxt.reset();
     int rc;
-    if ((rc = dice::dalloc_bytes(&c->d_wslots, slots.size() * 4)) || (rc = dice::dalloc_bytes(&c->d_wkeys, keys.size() * 16 + 16)) ||
-        (rc = dice::dalloc_bytes(&c->d_wlen, wlen.size() * 4 + 4)) || (rc = dice::dalloc_bytes(&c->d_woff, woff.size() * 4 + 4)) ||
-        (rc = dice::dalloc_bytes(&c->d_wtxt, txt.size() + 64)))
+    if ((rc = c->d_wslots.reserve(slots.size() * 4)) || (rc = c->d_wkeys.reserve(keys.size() * 16 + 16)) ||
+        (rc = c->d_wlen.reserve(wlen.size() * 4 + 4)) || (rc = c->d_woff.reserve(woff.size() * 4 + 4)) ||
+        (rc = c->d_wtxt.reserve(txt.size() + 64)))
         return rc;
     if (hipMemcpy(c->d_wslots, slots.data(), slots.size() * 4, hipMemcpyHostToDevice) != hipSuccess ||
         (n && hipMemcpy(c->d_wkeys, keys.data(), keys.size() * 16, hipMemcpyHostToDevice) != hipSuccess) ||
@@ -866,24 +837,17 @@ static int upload_text(dice_batch* b, bool utf8, int64_t n, const uint8_t* text,
         if (offsets[i] < 0 || (offsets[i] & 15) || text_len[i] < 0 || offsets[i] + text_len[i] > text_bytes)
             return fail(DICE_E_ARG, "file " + std::to_string(i) + ": offsets must be 16-byte aligned and inside the text");
     }
-    dice::WGuard g(c->device);
-    hipStream_t s = stream ? (hipStream_t)stream : c->stream;
+    dice::DeviceGuard g(c->device);
+    hipStream_t s = dice::stream_of(c, stream);
     int rc;
-    size_t cap8 = (size_t)b->capacity * 8, cap4 = (size_t)b->capacity * 4, cap1 = (size_t)b->capacity, capc = 16;
-    size_t tneed = (size_t)text_bytes + 64;   // (load32's slack past the last token)
-    if (tneed > b->text_cap) {
-        if (hipStreamSynchronize(s) != hipSuccess) return fail(DICE_E_DEVICE, "hipStreamSynchronize failed");
-        if ((rc = dice::grow(&b->d_text, b->text_cap, tneed))) return rc;
-    }
-    size_t dummy = 0;
-    if (!b->d_toff && (rc = dice::grow(&b->d_toff, dummy, cap8))) return rc;
-    if (!b->d_tlen && (rc = dice::grow(&b->d_tlen, dummy, cap4))) return rc;
-    if (!b->d_wstat && (rc = dice::grow(&b->d_wstat, dummy, cap1))) return rc;
-    if (!b->d_wcnt && (rc = dice::grow(&b->d_wcnt, dummy, capc))) return rc;
-    if (!b->d_fmask && (rc = dice::grow(&b->d_fmask, dummy, cap8))) return rc;
-    b->n = n;
-    b->n_long = 0;
-    ++b->epoch;
+    const size_t cap = (size_t)b->capacity;
+    // the text with load32's slack past the last token (the old buffer may still feed an earlier scan or
+    // hash: wait for the stream before it is freed); the counters {overflowed, long, next file, -}
+    if ((rc = b->d_text.reserve((size_t)text_bytes + 64, s)) || (rc = b->d_toff.reserve(cap)) ||
+        (rc = b->d_tlen.reserve(cap)) || (rc = b->d_wstat.reserve(cap)) || (rc = b->d_wcnt.reserve(4)) ||
+        (rc = b->d_fmask.reserve(cap)))
+        return rc;
+    dice::begin_upload(b, n);
     b->text_state = n == 0;   // (dice_batch_content_hash: the texts are resident once this call succeeds)
     b->text_utf8 = utf8;
     if (n_overflow) *n_overflow = 0;
@@ -902,11 +866,11 @@ static int upload_text(dice_batch* b, bool utf8, int64_t n, const uint8_t* text,
         hipMemsetAsync(b->d_text + text_bytes, 0, (size_t)(scan_bytes - text_bytes), s) != hipSuccess)
         return fail(DICE_E_DEVICE, "text upload failed");
     dice::VocabDev v;
-    v.slots = (const uint32_t*)c->d_wslots;
-    v.keys = (const uint4*)c->d_wkeys;
-    v.wmeta = (const uint32_t*)c->d_wlen;
-    v.woff = (const uint32_t*)c->d_woff;
-    v.wtxt = (const uint8_t*)c->d_wtxt;
+    v.slots = (const uint32_t*)c->d_wslots.get();
+    v.keys = (const uint4*)c->d_wkeys.get();
+    v.wmeta = (const uint32_t*)c->d_wlen.get();
+    v.woff = (const uint32_t*)c->d_woff.get();
+    v.wtxt = c->d_wtxt.get();
     v.bmask = c->words_bmask;
     v.id_bits = c->words_id_bits;
     v.V = (uint32_t)c->V;
@@ -956,8 +920,8 @@ int dice_batch_upload_text_utf8(dice_batch* b, int64_t n, const uint8_t* text, i
 int dice_batch_download_length(dice_batch* b, int32_t* length, void* stream) {
     if (!b) return fail(DICE_E_ARG, "NULL batch");
     dice_ctx* c = b->ctx;
-    dice::WGuard g(c->device);
-    hipStream_t s = stream ? (hipStream_t)stream : c->stream;
+    dice::DeviceGuard g(c->device);
+    hipStream_t s = dice::stream_of(c, stream);
     if (b->n && length && hipMemcpyAsync(length, b->d_len, (size_t)b->n * 4, hipMemcpyDeviceToHost, s) != hipSuccess)
         return fail(DICE_E_DEVICE, "length download failed");
     return hipStreamSynchronize(s) == hipSuccess ? DICE_OK : fail(DICE_E_DEVICE, "hipStreamSynchronize failed");
@@ -971,16 +935,14 @@ int dice_batch_set_rows(dice_batch* b, int64_t k, const int64_t* index, const ui
     for (int64_t j = 0; j < k; ++j)
         if (index[j] < 0 || index[j] >= b->n) return fail(DICE_E_ARG, "row index outside the batch");
     if (k == 0) return DICE_OK;
-    dice::WGuard g(c->device);
-    hipStream_t s = stream ? (hipStream_t)stream : c->stream;
+    dice::DeviceGuard g(c->device);
+    hipStream_t s = dice::stream_of(c, stream);
     int rc;
-    size_t dummy = 0;
-    if (!b->d_fmask && (rc = dice::grow(&b->d_fmask, dummy, (size_t)b->capacity * 8))) return rc;
+    if ((rc = b->d_fmask.reserve((size_t)b->capacity))) return rc;
     // staging: [index | wf | field masks | rows]
-    const size_t bytes = (size_t)k * (8 + 4 + 8 + (size_t)c->w64 * 8) + 64;
-    void* d = nullptr;
-    if ((rc = dice::dalloc_bytes(&d, bytes))) return rc;
-    char* p = (char*)d;
+    dice::DevBytes d;
+    if ((rc = d.reserve((size_t)k * (8 + 4 + 8 + (size_t)c->w64 * 8) + 64))) return rc;
+    char* p = (char*)d.get();
     int64_t* d_idx = (int64_t*)p;
     uint64_t* d_fm = (uint64_t*)(p + (size_t)k * 8);
     uint64_t* d_bits = (uint64_t*)(p + (size_t)k * 16);
@@ -994,11 +956,10 @@ int dice_batch_set_rows(dice_batch* b, int64_t k, const int64_t* index, const ui
                            field_mask ? d_fm : nullptr, c->w64, b->d_rows, b->d_wf, b->d_fmask);
         ok = hipGetLastError() == hipSuccess && hipStreamSynchronize(s) == hipSuccess;
     }
-    (void)hipFree(d);
+    d.reset();
     if (!ok) return fail(DICE_E_DEVICE, "row patch failed");
     if (c->kind == 3) {
-        if (c->prune)
-            for (int64_t j = 0; j < k; ++j) b->n_long += wordset_size[j] > c->prune_max_lf;
+        b->n_long += dice::count_long(c, wordset_size, k);
         return DICE_OK;
     }
     // the tile-layout kernels: repack (lengths and CC flags are already resident)
@@ -1023,8 +984,8 @@ int dice_batch_download_rows(dice_batch* b, uint64_t* bits, uint32_t* wordset_si
     if (!b) return fail(DICE_E_ARG, "NULL batch");
     dice_ctx* c = b->ctx;
     if (field_mask && b->n && !b->d_fmask) return fail(DICE_E_STATE, "the batch holds no field masks");
-    dice::WGuard g(c->device);
-    hipStream_t s = stream ? (hipStream_t)stream : c->stream;
+    dice::DeviceGuard g(c->device);
+    hipStream_t s = dice::stream_of(c, stream);
     const size_t n = (size_t)b->n;
     if (n && ((bits && hipMemcpyAsync(bits, b->d_rows, n * c->w64 * 8, hipMemcpyDeviceToHost, s) != hipSuccess) ||
               (wordset_size && hipMemcpyAsync(wordset_size, b->d_wf, n * 4, hipMemcpyDeviceToHost, s) != hipSuccess) ||
