@@ -277,9 +277,22 @@ int dice_exact(dice_ctx *ctx, const dice_files *files, const uint64_t *file_fiel
  * scan. dice_vocab_setup gives the context its vocabulary words in id order (n_words must equal
  * the V of dice_create; ASCII, distinct) and up to 64 extra words: the template field words
  * outside the vocabulary, numbered as licensee_host.h lh_template_field_masks numbers them, which
- * the scan reports as field-mask bits (what lh_prep_files' field_mask holds) instead of row bits. */
+ * the scan reports as field-mask bits (what lh_prep_files' field_mask holds) instead of row bits.
+ * A vocabulary of more than 251,904 words (dice_words64(V) > 3,936: the scan's workgroup would need
+ * more than the 160 KiB of LDS a CU has) is refused with DICE_E_ARG. Measured on an MI355X under
+ * ROCm 7.2.0: the launch with 160 KiB of dynamic LDS is granted without an opt-in attribute and
+ * scans correctly (tests/test_gpu_words_edges.py, test_largest_vocabulary). */
 int dice_vocab_setup(dice_ctx *ctx, int32_t n_words, const char *const *words, int32_t n_extra,
                      const char *const *extra);
+/* The two facts of dice_vocab_setup's table a caller needs to aim an input at it; host code, no
+ * context or device needed, and dice_vocab_setup itself calls both. dice_words_key_hash: the 64-bit
+ * hash of a word's key (its first 16 bytes, its length and, past 16 bytes, the FNV-1a hash of the
+ * rest). A word's home bucket is hash & (n_buckets - 1), its tag is hash >> 40 cut to 32 - id_bits
+ * bits, and its home slot in a wave's set of non-vocabulary words is hash & 255.
+ * dice_vocab_geometry: the table's bucket count (a power of two, 8 slots each) and the bits of a
+ * slot's id field for n_total = n_words + n_extra words. */
+int dice_words_key_hash(const uint8_t *word, int32_t len, uint64_t *hash);
+int dice_vocab_geometry(int32_t n_total, int32_t *n_buckets, int32_t *id_bits);
 /* text[0, text_bytes): the batch's normalized texts as bytes (every non-ASCII character one byte
  * >= 0x80), file i at text[offsets[i], offsets[i] + text_len[i]), offsets 16-byte aligned (the
  * last file may end exactly at text_bytes: no padding has to follow it);

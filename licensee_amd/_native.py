@@ -36,6 +36,7 @@ EXPORTED_SYMBOLS = (
     'dice_topk', 'dice_topk_sharded', 'dice_batch_topk', 'dice_batch_download_topk', 'dice_batch_matrix_bytes',
     'dice_batch_upload_text_utf8', 'dice_batch_download_length',
     'dice_batch_projects', 'dice_batch_download_projects', 'dice_batch_download_project_match',
+    'dice_words_key_hash', 'dice_vocab_geometry',
 )
 DICE_GATHER_HOST = 0
 DICE_GATHER_DEVICE = 1
@@ -208,6 +209,8 @@ def load_library(path: str = LIB_PATH) -> ctypes.CDLL:
         'dice_batch_download_exact': (ctypes.c_int, [vp, vp, vp]),
         'dice_exact': (ctypes.c_int, [vp, ctypes.POINTER(_Files), vp, vp]),
         'dice_vocab_setup': (ctypes.c_int, [vp, i32, vp, i32, vp]),
+        'dice_words_key_hash': (ctypes.c_int, [vp, i32, vp]),
+        'dice_vocab_geometry': (ctypes.c_int, [i32, vp, vp]),
         'dice_batch_upload_text': (ctypes.c_int, [vp, i64, vp, i64, vp, vp, vp, vp, vp, ctypes.POINTER(i64), vp]),
         'dice_batch_upload_text_utf8': (ctypes.c_int, [vp, i64, vp, i64, vp, vp, vp, vp, vp, ctypes.POINTER(i64), vp]),
         'dice_batch_download_length': (ctypes.c_int, [vp, vp, vp]),

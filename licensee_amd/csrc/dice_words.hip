@@ -749,6 +749,27 @@ using dice::fail;
 
 extern "C" {
 
+int dice_words_key_hash(const uint8_t* word, int32_t len, uint64_t* hash) {
+    if (!word || len <= 0 || !hash) return fail(DICE_E_ARG, "invalid word");
+    uint64_t lo, hi;
+    uint32_t tail;
+    dice::host_key(std::string(reinterpret_cast<const char*>(word), (size_t)len), lo, hi, tail);
+    *hash = dice::words_mix(lo, hi, (uint32_t)len, tail);
+    return DICE_OK;
+}
+
+int dice_vocab_geometry(int32_t n_total, int32_t* n_buckets, int32_t* id_bits) {
+    if (n_total < 0 || !n_buckets || !id_bits) return fail(DICE_E_ARG, "invalid vocabulary size");
+    size_t nb = 2;
+    while (nb * dice::kSlots < 2 * (size_t)n_total + 1) nb <<= 1;
+    int32_t bits = 1;
+    while (((uint64_t)1 << bits) <= (uint64_t)n_total + 1) ++bits;
+    if (bits > 28) return fail(DICE_E_ARG, "too many words");
+    *n_buckets = (int32_t)nb;
+    *id_bits = bits;
+    return DICE_OK;
+}
+
 int dice_vocab_setup(dice_ctx* c, int32_t n_words, const char* const* words, int32_t n_extra,
                      const char* const* extra) {
     if (!c) return fail(DICE_E_ARG, "NULL ctx");
@@ -766,23 +787,24 @@ int dice_vocab_setup(dice_ctx* c, int32_t n_words, const char* const* words, int
         for (unsigned char ch : w[(size_t)i])
             if (ch >= 0x80) return fail(DICE_E_ARG, "words are ASCII (the wordset scan's [\\w/-])");
     }
-    size_t nb = 2;
-    while (nb * dice::kSlots < 2 * (size_t)n + 1) nb <<= 1;
-    uint32_t id_bits = 1;
-    while (((uint64_t)1 << id_bits) <= (uint64_t)n + 1) ++id_bits;
-    if (id_bits > 28) return fail(DICE_E_ARG, "too many words");
+    int32_t n_buckets, id_bits_i;
+    if (int rc = dice_vocab_geometry(n, &n_buckets, &id_bits_i)) return rc;
+    const size_t nb = (size_t)n_buckets;
+    const uint32_t id_bits = (uint32_t)id_bits_i;
     std::vector<uint32_t> slots(nb * dice::kSlots, 0), wlen((size_t)n), woff((size_t)n);
     std::vector<uint4> keys((size_t)n);
     std::string txt;
     for (int32_t i = 0; i < n; ++i) {
-        uint64_t lo, hi;
+        uint64_t lo, hi, h;
         uint32_t tail;
         dice::host_key(w[(size_t)i], lo, hi, tail);
         keys[(size_t)i] = make_uint4((uint32_t)lo, (uint32_t)(lo >> 32), (uint32_t)hi, (uint32_t)(hi >> 32));
         wlen[(size_t)i] = (uint32_t)w[(size_t)i].size();
         woff[(size_t)i] = (uint32_t)txt.size();
         txt += w[(size_t)i];
-        const uint64_t h = dice::words_mix(lo, hi, wlen[(size_t)i], tail);
+        if (int rc = dice_words_key_hash(reinterpret_cast<const uint8_t*>(w[(size_t)i].data()),
+                                         (int32_t)w[(size_t)i].size(), &h))
+            return rc;
         const uint32_t tag = ((uint32_t)(h >> 40)) << id_bits;
         for (size_t b = h & (nb - 1);; b = (b + 1) & (nb - 1)) {
             uint32_t* r = slots.data() + b * dice::kSlots;
